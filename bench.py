@@ -15,9 +15,17 @@ BASELINE.json's configs[1] names.  Same MFMA rate, same bytes: the headline runs
 Inputs are resident in HBM before the timed region.  Secondary metric (same JSON line, key "cbir"): CBIR query-pairs/s,
 10k queries x 1M gallery, D=128, k=100 (configs[3] on one GPU; at N > 1 the gallery is row-sharded over the ranks, 125 k rows each at N = 8).
 
-Prints ONE JSON line on rank 0 (driver contract) with `roofline` (dominant kernel: the bf16 GEMM, timed live with HIP events
-on its launch stream inside the timed region) and `cpu_baseline` (the oracle restatement timed on this box's host cores,
-bounded sample, rank 0 at N=1 only).
+Prints ONE JSON line on rank 0 (driver contract).  A plain run does only what the headline needs: set up, W warm-up steps, K timed steps
+(`ms_per_step` = their wall time / K), the outputs of the last step if --dump-outputs DIR is given, the line.  --full adds everything else,
+as the default run did before the option existed: `roofline.dominant_kernel` (the 16-bit GEMM family, timed live with HIP events on its
+launch stream inside the timed region -- the events cost the timed steps ~0.2 ms each), the parity legs, the other operand format,
+`cpu_baseline` (the oracle restatement timed on the host cores, bounded sample), cfg5, swin, cfg3, the CBIR leg and, at N > 1, the sharded
+search and the RCCL topology lines; the --no-* switches drop single legs of a --full run.
+
+--dump-outputs DIR writes, after the timed steps, what the timed path handed its caller in the last step, from rank 0, as float32 .npy:
+loss_rows (the per-image losses FusedTrainStep.step returns), params_sample / ema_sample (the flat fp32 master weights and the EMA weights
+at a fixed, seeded sample of DUMP_SAMPLE positions) and, on fp16 operands, loss_state (GradScaler scale, growth tracker, skipped steps).
+The inputs (weights, images, labels) are seeded: the same arguments give the same inputs on every run and every build.
 """
 from __future__ import annotations
 
@@ -92,6 +100,7 @@ def parity_vit(be, dev, operand="fp16"):
 
 
 GEMM_EVENT_STRIDE = 4      # steps between two event-timed steps of the timed region
+DUMP_SAMPLE = 1 << 22      # weight positions written by --dump-outputs (16 MB per array)
 
 
 def pmc_traffic_per_launch():
@@ -412,10 +421,11 @@ def _max_over_ranks(dt: float, world: int, dev) -> float:
 
 
 def train_leg(be, dev, rank: int, world: int, steps: int, warmup: int, batch: int, spec=None, img: int = 224, classes: int = 1000, events: bool = True,
-              bucket_bytes: int = 24 << 20, operand: str = "bf16"):
+              bucket_bytes: int = 24 << 20, operand: str = "bf16", outputs: dict | None = None):
     """Hot path A on this rank (one process per GPU): W warm-up steps, barrier + sync, K timed steps, sync + barrier, MAX over ranks.
     Returns (seconds for K steps, final loss, gemm event totals or None, collectives issued).  N > 1: the flat gradient leaves in buckets from inside the backward
-    (visiondk_amd/comm.py), overlapped with the remaining backward kernels.  The same function runs on CPU over gloo with the emulated kernels (tests/test_ddp_gloo.py)."""
+    (visiondk_amd/comm.py), overlapped with the remaining backward kernels.  The same function runs on CPU over gloo with the emulated kernels (tests/test_ddp_gloo.py).
+    `outputs` (a dict) receives, after the timing, the host copies --dump-outputs writes (last_step_outputs)."""
     from visiondk_amd import comm as vcomm, vit
     if spec is None:
         spec = vit.spec_from_timm_name("vit_base_patch16_224", classes)
@@ -435,10 +445,11 @@ def train_leg(be, dev, rank: int, world: int, steps: int, warmup: int, batch: in
         be.check(be.lib.vdk_prof_begin(launches_per_step * steps + 64), "vdk_prof_begin")
     _sync(dev)
     t0 = time.perf_counter()
+    rows = None
     for it in range(steps):
         if ev:      # every GEMM launch of every 4th timed step carries a (start, stop) event pair: a timed dispatch costs ~5 us of queue time, 0.7-1.0 ms per step if all 149 are timed
             be.lib.vdk_prof_pause(0 if it % GEMM_EVENT_STRIDE == 0 else 1)
-        step.step(x, y)
+        rows = step.step(x, y)
     _sync(dev); _barrier(world)
     dt = time.perf_counter() - t0
     gemm = None
@@ -452,8 +463,38 @@ def train_leg(be, dev, rank: int, world: int, steps: int, warmup: int, batch: in
     ncoll = comm.collectives if comm is not None else 0
     if gemm is not None and step.amp:
         gemm["loss_scale"] = step.loss_scale(); gemm["skipped_steps"] = step.skipped_steps()
+    if outputs is not None:
+        outputs.update(last_step_outputs(step, rows))
     del step, model
     return dt, loss, gemm, ncoll
+
+
+def last_step_outputs(step, rows) -> dict:
+    """what FusedTrainStep hands its caller after the last step, as float32 host arrays: the per-image losses it returned, the fp32 master weights and the EMA
+    weights (at DUMP_SAMPLE positions drawn from a fixed seed, sorted; all of them when there are fewer), the GradScaler state on fp16 operands"""
+    params = step.eng.params
+    n = params.numel()
+    if n <= DUMP_SAMPLE:
+        idx = torch.arange(n)
+    else:
+        g = torch.Generator(device="cpu"); g.manual_seed(0)
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+    idx = idx.to(params.device)
+    out = {"params_sample": params.reshape(-1)[idx]}
+    if rows is not None:
+        out["loss_rows"] = rows
+    if step.ema is not None:
+        out["ema_sample"] = step.ema.reshape(-1)[idx]
+    if step.loss_state is not None:
+        out["loss_state"] = step.loss_state
+    return {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(outdir: str, arrays: dict) -> None:
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cbir_sharded_leg(be, dev, rank: int, world: int, nq: int = 10000, n: int = 1_000_000, d: int = 128, k: int = 100, iters: int = 6, warm: int = 3, cap=None,
@@ -542,6 +583,11 @@ def main():
     ap.add_argument("--operand", choices=("fp16", "bf16"), default="fp16",
                     help="16-bit operand format of the headline leg: fp16 = the reference's autocast dtype + GradScaler (train.py:118,205-211), bf16 = BASELINE.json configs[1]'s word; the other one is timed beside it")
     ap.add_argument("--no-other-operand", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: GEMM event timing (roofline.dominant_kernel), parity, the other operand, cpu_baseline, cfg5, swin, cfg3, CBIR "
+                         "(the --no-* switches drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (rank 0) to DIR/<name>.npy, float32")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -562,7 +608,7 @@ def main():
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("NCCL_MAX_NCHANNELS", "32")      # = the CUs GradAllReduce keeps out of the persistent GEMM grids (profiles/r03_w4_contention.json)
-        if rank == 0 and "NCCL_DEBUG" not in os.environ:      # the rings / trees RCCL builds over xGMI, quoted in the JSON line (rank 0's log only)
+        if args.full and rank == 0 and "NCCL_DEBUG" not in os.environ:      # the rings / trees RCCL builds over xGMI, quoted in the JSON line (rank 0's log only)
             import tempfile
             rccl_log = os.path.join(tempfile.gettempdir(), f"vdk_rccl_{os.getpid()}.log")
             os.environ.update({"NCCL_DEBUG": "INFO", "NCCL_DEBUG_SUBSYS": "INIT,GRAPH", "NCCL_DEBUG_FILE": rccl_log})
@@ -574,15 +620,20 @@ def main():
     be = _lib.load()
 
     other = "bf16" if args.operand == "fp16" else "fp16"
-    parity = parity_vit(be, dev, args.operand) if (world == 1 and rank == 0 and not args.no_parity) else None
+    full = args.full
+    parity = parity_vit(be, dev, args.operand) if (full and world == 1 and rank == 0 and not args.no_parity) else None
     parity_other = parity_vit(be, dev, other) if (parity is not None and not args.no_other_operand) else None
-    dt, loss, gemm, ncoll = train_leg(be, dev, rank, world, args.steps, args.warmup, args.batch, operand=args.operand)
+    outputs = {} if (args.dump_outputs and rank == 0) else None
+    dt, loss, gemm, ncoll = train_leg(be, dev, rank, world, args.steps, args.warmup, args.batch, events=full, operand=args.operand, outputs=outputs)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
+        del outputs
     leg2 = None
-    if world == 1 and not args.no_other_operand:      # the other operand format, same box, same steps, right after the headline leg
+    if full and world == 1 and not args.no_other_operand:      # the other operand format, same box, same steps, right after the headline leg
         torch.cuda.empty_cache()
         leg2 = train_leg(be, dev, rank, world, args.steps, args.warmup, args.batch, operand=other)
     cbir_n = None
-    if world > 1 and not args.no_cbir:
+    if full and world > 1 and not args.no_cbir:
         torch.cuda.empty_cache()
         cbir_n = cbir_sharded_leg(be, dev, rank, world)
 
@@ -637,18 +688,18 @@ def main():
             out["parity"] = parity
         if parity_other is not None:
             out["parity_other_operand"] = parity_other
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_vit()
-        if world == 1 and not args.no_cfg5:
+        if full and world == 1 and not args.no_cfg5:
             torch.cuda.empty_cache()
             out["cfg5"] = bench_cfg5(be, dev)
-        if world == 1 and not args.no_swin:
+        if full and world == 1 and not args.no_swin:
             torch.cuda.empty_cache()
             out["swin"] = bench_swin(be, dev)
-        if world == 1 and not args.no_cfg3:
+        if full and world == 1 and not args.no_cfg3:
             torch.cuda.empty_cache()
             out["cfg3"] = bench_cfg3(be, dev)
-        if world == 1 and not args.no_cbir:
+        if full and world == 1 and not args.no_cbir:
             torch.cuda.empty_cache()
             out["cbir"] = bench_cbir(dev, with_cpu=not args.no_cpu_baseline)
         elif cbir_n is not None:

@@ -1,13 +1,14 @@
 """The drop-in boundary proven with the reference's OWN code.
 
-* `index()` / `search()` of /root/reference/engine/cbir/evaluation.py (lines 106-200) are read at test time, exec'd into a namespace whose `faiss` is
+* `index()` / `search()` of the reference's engine/cbir/evaluation.py (lines 106-200) are read at test time, exec'd into a namespace whose `faiss` is
   visiondk_amd.faiss_shim and whose extractor is visiondk_amd.face.FeatureExtractor, and must return the oracle's scores / indices bit for bit.
-* `Trainer.update` of /root/reference/engine/procedure/train.py (lines 203-215) is exec'd as it stands and drives visiondk_amd.vit.VisionTransformer with the stock
+* `Trainer.update` of the reference's engine/procedure/train.py (lines 203-215) is exec'd as it stands and drives visiondk_amd.vit.VisionTransformer with the stock
   torch.optim.SGD, torch's GradScaler and the reference's own ModelEMA (models/ema.py, loaded by path).
 
-Nothing of the reference is copied into the repository: the functions are cut out of the source files with `ast` when the tests run.  /root/reference does not exist on the
-GPU box: those tests skip there, and the committed fixture tests/golden/faiss_shim_reference_run.npz (written by tests/golden/make_faiss_shim_golden.py from a run of the
-reference's functions over the shim) pins the same numbers for the `-m gpu` run."""
+Nothing of the reference is committed to the repository: build() stages those files into the git-ignored oracle/_ref/ (oracle/ref_stage.py) and the functions are
+cut out of them with `ast` when the tests run.  Where the reference could not be staged, those tests skip, and the committed fixture
+tests/golden/faiss_shim_reference_run.npz (written by tests/golden/make_faiss_shim_golden.py from a run of the reference's functions over the shim) pins the same
+numbers, on the emulator and for the `-m gpu` run."""
 import ast
 import importlib.util
 import textwrap
@@ -17,12 +18,13 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import cbir as ocbir
+from oracle import cbir as ocbir, ref_stage
 from visiondk_amd import cbir, faiss_shim
 
-REF = Path("/root/reference")
+REF = ref_stage.STAGE          # the reference's files as build() staged them, at their paths relative to the reference's root
 GOLD = Path(__file__).resolve().parent / "golden" / "faiss_shim_reference_run.npz"
-needs_ref = pytest.mark.skipif(not REF.exists(), reason="/root/reference is not present on this box")
+REF_STAGED = all(ref_stage.staged(f) is not None for f in ("engine/cbir/evaluation.py", "engine/procedure/train.py", "models/ema.py"))
+needs_ref = pytest.mark.skipif(not REF_STAGED, reason="the reference's files were not staged into oracle/_ref by build() (reference checkout absent or unreadable)")
 
 
 def _cut(path: Path, names, cls=None) -> str:
@@ -262,13 +264,13 @@ TRAINER_GOLD = Path(__file__).resolve().parent / "golden" / "trainer_update_refe
 @pytest.mark.parametrize("operand", ["fp16", "bf16"])
 def test_committed_trainer_update_fixture(be, dev, operand):
     """tests/golden/trainer_update_reference_run.npz (written by make_trainer_update_golden.py from the reference's own Trainer.update on the fp32 PyTorch-CPU path: three
-    steps of scaler.scale(loss).backward / unscale_ / clip / step / update / ema.update) against the HIP library's step on the same seeds -- on the emulator and, where
-    /root/reference does not exist, on the MI355X: the loss sequence and the final weights of every parameter.  fp16 operands (the reference's autocast dtype) with the
+    steps of scaler.scale(loss).backward / unscale_ / clip / step / update / ema.update) against the HIP library's step on the same seeds -- on the MI355X and, where
+    the reference's files are not staged, on the emulator: the loss sequence and the final weights of every parameter.  fp16 operands (the reference's autocast dtype) with the
     GradScaler protocol at the fixture's initial scale; bf16 beside it with its 8x coarser bounds."""
     from oracle.vit_ref import VisionTransformerRef
     from visiondk_amd import vit
-    if not be.device_only and (operand == "bf16" or REF.exists()):
-        pytest.skip("on the emulator the reference's update() itself drives the library (test_reference_trainer_update_drives_the_hip_vit) where /root/reference exists; "
+    if not be.device_only and (operand == "bf16" or REF_STAGED):
+        pytest.skip("on the emulator the reference's update() itself drives the library (test_reference_trainer_update_drives_the_hip_vit) where its files are staged; "
                     "the recorded run is for the GPU box, and for an emulator run without the reference (fp16 arm)")
     z = np.load(TRAINER_GOLD)
     c = {k[4:]: float(z[k]) for k in z.files if k.startswith("cfg_")}
