@@ -543,13 +543,14 @@ __device__ __forceinline__ float cbir_eps(const float* __restrict__ qn3, long q,
 // `m` = the lane's maximum over the block (the cheap reject that precedes this).  Only lanes that own a survivor build their row mask; slots are handed out lane by
 // lane through SGPRs (v_readlane of each owner's count): no atomics, no LDS round trip on the wave's critical path.  A survivor travels with its approximate score
 // (the approximate-ranking schedule ranks on it): an owner's only survivor -- the usual case -- IS its maximum `m`; the value of any other one comes from a
-// select chain over the 16 registers (a lane-dependent register index has no cheaper form).  LAST: the tile may reach past r_end (rows there are clamped copies).
+// select chain over the 16 registers (a lane-dependent register index has no cheaper form).  LAST: the tile may reach past r_end -- the rows there are clamped
+// copies of row r_end - 1, masked out of PM but not out of `m`, so a lone survivor beside them is NOT the maximum: last tiles always take the select chain.
 // (round 6, measured and dropped: one v_cmp per register into scalar masks, OR-ed on the scalar unit, with the emission under per-register scalar branches -- the
 //  score then has a static register index -- was 0.5 ms SLOWER per search: the taken branches of the survivor path cost more than the per-lane masks here.)
-#define CF_EMIT_OWNED(ACC, PM, POS, QL, ROWB)                                                                                                      \
+#define CF_EMIT_OWNED(ACC, PM, POS, QL, ROWB, LAST)                                                                                                \
   do {                                                                                                                                            \
     unsigned mm_ = (PM);                                                                                                                          \
-    const bool single_ = (mm_ & (mm_ - 1u)) == 0u;                                                                                                 \
+    const bool single_ = !(LAST) && (mm_ & (mm_ - 1u)) == 0u;                                                                                      \
     while (mm_) {                                                                                                                                 \
       const int r = 15 - (__ffs(mm_) - 1);      /* CF_ROWBIT */                                                                                   \
       mm_ &= mm_ - 1;                                                                                                                             \
@@ -584,7 +585,7 @@ __device__ __forceinline__ float cbir_eps(const float* __restrict__ qn3, long q,
     if (wcnt + tot_ > CF_WE) { CF_FLUSH(); }                                                                                                       \
     if (tot_ <= CF_WE) {                                                                                                                          \
       unsigned pos = wcnt + pre_;                                                                                                                 \
-      if (c) CF_EMIT_OWNED(ACC, pm, pos, QL, ROWB);                                                                                               \
+      if (c) CF_EMIT_OWNED(ACC, pm, pos, QL, ROWB, LAST);                                                                                         \
       wcnt += tot_;                                                                                                                               \
     } else {   /* more survivors in one block than the staging holds (a pass-everything stage): lane by lane, flushing in between */              \
       unsigned long long bl = __ballot(c != 0);                                                                                                   \
@@ -593,14 +594,14 @@ __device__ __forceinline__ float cbir_eps(const float* __restrict__ qn3, long q,
         const int L = __ffsll(b) - 1;                                                                                                             \
         const unsigned cL = (unsigned)VDK_READLANE(c, L);                                                                                         \
         if (wcnt + cL > CF_WE) {   /* stage what was granted so far, then flush (uniform branch) */                                               \
-          if (c && (bl & ~b & (1ull << lane))) { unsigned pp = pos; CF_EMIT_OWNED(ACC, pm, pp, QL, ROWB); }                                        \
+          if (c && (bl & ~b & (1ull << lane))) { unsigned pp = pos; CF_EMIT_OWNED(ACC, pm, pp, QL, ROWB, LAST); }                                  \
           bl = b;   /* owners before L are done */                                                                                                \
           CF_FLUSH();                                                                                                                             \
         }                                                                                                                                         \
         if (lane == L) pos = wcnt;                                                                                                                \
         wcnt += cL;                                                                                                                               \
       }                                                                                                                                           \
-      if (c && (bl & (1ull << lane))) CF_EMIT_OWNED(ACC, pm, pos, QL, ROWB);                                                                       \
+      if (c && (bl & (1ull << lane))) CF_EMIT_OWNED(ACC, pm, pos, QL, ROWB, LAST);                                                                 \
     }                                                                                                                                             \
   } while (0)
 #define CF_NBUF 3
