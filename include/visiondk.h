@@ -348,6 +348,11 @@ int vdk_gemm_f32_nt(const VdkGemmF32Desc* d, void* stream);
 int vdk_window_attention_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, const float* bias, const float* mask, int32_t nW, int64_t windows, int32_t H, int32_t N,
                              int32_t hd, float scale, const int32_t* rowidx, void* ws, size_t ws_bytes, void* stream);
 int vdk_window_attention_fwd_workspace_bytes(int32_t nW, int32_t H, size_t* bytes);   /* nW = 0 without a mask */
+/* The same step of timm's WindowAttention (inside SwinTransformerBlock) for the PRECISE path: qkv / o f32 (ld, ldo % 4 == 0, 16-byte aligned), both contractions on the fp32
+ * MFMA, library expf and a true division in the softmax, no lse (evaluation only).  Same arguments, refusals and workspace (vdk_window_attention_fwd_workspace_bytes) as
+ * the 16-bit entry. */
+int vdk_window_attention_fwd_f32(const float* qkv, int64_t ld, float* o, int64_t ldo, const float* bias, const float* mask, int32_t nW, int64_t windows, int32_t H, int32_t N,
+                                 int32_t hd, float scale, const int32_t* rowidx, void* ws, size_t ws_bytes, void* stream);
 int vdk_window_attention_bwd_workspace_bytes(int64_t windows, int32_t nW, int32_t H, size_t* bytes);
 int vdk_window_attention_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, const float* bias, const float* mask, int32_t nW,
                              int64_t windows, int32_t H, int32_t N, int32_t hd, float scale, const int32_t* rowidx, void* dqkv, int64_t ldd, float* dbias, void* ws,
@@ -595,6 +600,11 @@ int vdk_swin_workspace_bytes(const VdkSwinConfig* cfg, size_t* bytes);
 int vdk_swin_refresh_weights(const VdkSwinConfig* cfg, const float* params, void* wb16, void* wt16, int32_t skip_wb16, void* stream);
 /* x f32 [B, in_chans, img, img] -> out f32: logits [B, up(num_classes, 8)] or the feature rows (see above); activations stay in ws */
 int vdk_swin_forward(const VdkSwinConfig* cfg, const float* x, const float* params, const void* wb16, void* ws, size_t ws_bytes, float* out, void* stream);
+/* PRECISE forward, as vdk_vit_forward_f32: every contraction on the fp32 MFMA over the fp32 master weights `params`, fp32 activations, window attention by
+ * vdk_window_attention_fwd_f32; nothing is kept for a backward, cfg->drop_path is ignored (evaluation) and cfg->operand selects nothing.  Output as vdk_swin_forward.  The workspace is a
+ * ping-pong plan of its own (vdk_swin_workspace_f32_bytes) that does not grow with the depths. */
+int vdk_swin_workspace_f32_bytes(const VdkSwinConfig* cfg, size_t* bytes);
+int vdk_swin_forward_f32(const VdkSwinConfig* cfg, const float* x, const float* params, void* ws, size_t ws_bytes, float* out, void* stream);
 /* dout: dlogits bf16 [B, up(num_classes, 8)] (padding columns zero), or f32 feature-row gradients -> grads (flat fp32, overwritten); on_ready as in vdk_vit_backward.
  * `grads` must be ZERO-INITIALISED ONCE by its owner: every tensor's gradient is overwritten by each call, but the alignment gaps of the flat layout (tensors start at multiples
  * of 64 floats: the 96 / 192-wide vectors and the 169 x heads tables leave some) are never written, and vdk_sumsq_f32 (the clip norm), vdk_allreduce_bucket and the fp16

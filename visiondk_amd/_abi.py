@@ -177,6 +177,7 @@ SIGNATURES: dict[str, tuple] = {
     "vdk_softmax_rows_f32": (C.c_int, [P, I64, I64, I32, C.c_float, P]),
     "vdk_window_attention_fwd": (C.c_int, [P, I64, P, I64, P, P, P, I32, I64, I32, I32, I32, F32, P, P, SZ, P]),
     "vdk_window_attention_fwd_workspace_bytes": (C.c_int, [I32, I32, PSZ]),
+    "vdk_window_attention_fwd_f32": (C.c_int, [P, I64, P, I64, P, P, I32, I64, I32, I32, I32, F32, P, P, SZ, P]),
     "vdk_relpos_bias_table_grad": (C.c_int, [P, P, I32, I32, I32, I32, P, P]),
     "vdk_window_attention_bwd_workspace_bytes": (C.c_int, [I64, I32, I32, PSZ]),
     "vdk_window_attention_bwd": (C.c_int, [P, I64, P, P, I64, P, P, P, I32, I64, I32, I32, I32, F32, P, P, I64, P, P, SZ, P]),
@@ -230,6 +231,8 @@ SIGNATURES: dict[str, tuple] = {
     "vdk_preprocess_resize_pad_normalize": (C.c_int, [P, P, P, I32, I32, I32, F32, F32, F32, F32, F32, F32, P, P, P, SZ, P]),
     "vdk_vit_workspace_f32_bytes": (C.c_int, [C.POINTER(VitConfig), PSZ]),
     "vdk_vit_forward_f32": (C.c_int, [C.POINTER(VitConfig), P, P, P, SZ, P, P]),
+    "vdk_swin_workspace_f32_bytes": (C.c_int, [C.POINTER(SwinConfig), PSZ]),
+    "vdk_swin_forward_f32": (C.c_int, [C.POINTER(SwinConfig), P, P, P, SZ, P, P]),
     "vdk_convnext_workspace_f32_bytes": (C.c_int, [C.POINTER(ConvNextConfig), PSZ]),
     "vdk_convnext_forward_f32": (C.c_int, [C.POINTER(ConvNextConfig), P, P, P, P, SZ, P, P]),
     "vdk_convnext_train_f32_workspace_bytes": (C.c_int, [C.POINTER(ConvNextConfig), PSZ]),

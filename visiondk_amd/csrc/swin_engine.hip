@@ -677,3 +677,124 @@ int vdk_swin_backward(const VdkSwinConfig* cfg, const void* dout, const float* p
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// PRECISE forward (evaluation / embedding extraction), as vit_engine.hip's: the same network with every contraction on the fp32 MFMA (csrc/gemm_f32.hip), fp32 activations
+// throughout and the fused fp32 window attention (csrc/window_attention_f32.hip: S and P never leave the registers).  Reads the fp32 master weights directly; nothing is
+// saved for a backward, so the workspace is a ping-pong plan sized by the largest stage: the residual stream alternates between xa and xb, h / qkv / o / u are reused by
+// every block, and ONE additive attention tile is prepared in front of each block's attention instead of one per block for the whole call.
+extern "C" {
+int vdk_gemm_f32_nt(const VdkGemmF32Desc*, void*);
+int vdk_patchify_f32(const float*, int32_t, int32_t, int32_t, int32_t, int32_t, float*, void*);
+}
+int vdk_wa_fwd_f32_bm(const float* qkv, int64_t ld, float* o, int64_t ldo, const float* bm, int32_t nWm, int64_t windows, int32_t H, float scale, const int32_t* rowidx, void* stream);
+
+namespace {
+struct StageW32 { size_t rowidx0, rowidx3, mask; };
+struct WsF32 { size_t total, patches, xa, xb, h, qkv, o, u, bm, pooled; StageW32 st[4]; };
+void sw_plan_f32(const SwDims& d, WsF32* w) {
+  size_t cur = 0, maxTD = 0, maxTM = 0, maxbm = 0;
+  for (int i = 0; i < d.nst; ++i) {
+    const size_t T = (size_t)d.T[i], C = d.dim[i];
+    const int nW = (d.res[i] / SW_WS) * (d.res[i] / SW_WS);
+    w->st[i].rowidx0 = w_take(cur, T * 4);
+    w->st[i].rowidx3 = w->st[i].mask = 0;
+    if (d.res[i] > SW_WS) { w->st[i].rowidx3 = w_take(cur, T * 4); w->st[i].mask = w_take(cur, (size_t)nW * SW_N * SW_N * 4); }
+    if (T * C > maxTD) maxTD = T * C;            // (the PatchMerging operand in front of stage i has T_i * 4 C_{i-1} = T_{i-1} * C_{i-1} values: covered by stage i - 1)
+    if (T * 4 * C > maxTM) maxTM = T * 4 * C;
+    const size_t bm = vdk_wa_bm_bytes(d.res[i] > SW_WS ? nW : 0, d.heads[i]); if (bm > maxbm) maxbm = bm;
+  }
+  w->patches = w_take(cur, (size_t)d.T[0] * d.Kpe * 4);
+  w->xa = w_take(cur, maxTD * 4); w->xb = w_take(cur, maxTD * 4); w->h = w_take(cur, maxTD * 4);
+  w->qkv = w_take(cur, maxTD * 3 * 4); w->o = w_take(cur, maxTD * 4); w->u = w_take(cur, maxTM * 4);
+  w->bm = w_take(cur, maxbm);
+  w->pooled = w_take(cur, (size_t)d.B * d.dim[d.nst - 1] * 4);
+  w->total = cur;
+}
+int gemm32(hipStream_t s, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N, int K, const float* bias, const float* res, int64_t ldr, int act) {
+  VdkGemmF32Desc g = {};
+  g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.bias = bias; g.residual = res; g.ldr = ldr; g.act = act; g.alpha = 1.0f;
+  return vdk_gemm_f32_nt(&g, s);
+}
+}  // namespace
+
+extern "C" {
+
+int vdk_swin_workspace_f32_bytes(const VdkSwinConfig* cfg, size_t* bytes) {
+  SwDims d; RC(sw_dims(cfg, &d));
+  if (!bytes) return vdk_fail(VDK_EINVAL, "null");
+  WsF32 w; sw_plan_f32(d, &w);
+  *bytes = w.total;
+  return VDK_OK;
+}
+
+// x: f32 [B, Cin, img, img] -> out f32: logits [B, Cp] or, in feature mode (num_classes = 0), the normed NHWC map [B * 49 * (img / 224)^2, D], as vdk_swin_forward
+int vdk_swin_forward_f32(const VdkSwinConfig* cfg, const float* x, const float* params, void* ws, size_t ws_bytes, float* out, void* stream_) {
+  hipStream_t s = (hipStream_t)stream_;
+  SwDims d; RC(sw_dims(cfg, &d));
+  PLayout p; sw_layout(d, &p);
+  WsF32 w; sw_plan_f32(d, &w);
+  if (!x || !params || !ws || !out) return vdk_fail(VDK_EINVAL, "vdk_swin_forward_f32: null pointer");
+  if (ws_bytes < w.total) return vdk_fail(VDK_EWORKSPACE, "vdk_swin_forward_f32: workspace too small");
+  char* base = (char*)ws;
+  float* patches = (float*)(base + w.patches);
+  float* xa = (float*)(base + w.xa); float* xb = (float*)(base + w.xb); float* h = (float*)(base + w.h);
+  float* qkv = (float*)(base + w.qkv); float* o = (float*)(base + w.o); float* u = (float*)(base + w.u);
+  float* bm = (float*)(base + w.bm);
+  {      // the window-partition row indices and shift masks of this batch size: one launch
+    SwTables t; t.n = 0; t.total = 0;
+    auto seg = [&](void* out_, long count, int kind, int res, int shift) { t.seg[t.n++] = SwTableSeg{t.total, out_, kind, d.B, res, shift}; t.total += count; };
+    for (int i = 0; i < d.nst; ++i) {
+      seg(base + w.st[i].rowidx0, d.T[i], 0, d.res[i], 0);
+      if (d.res[i] > SW_WS) {
+        seg(base + w.st[i].rowidx3, d.T[i], 0, d.res[i], SW_WS / 2);
+        seg(base + w.st[i].mask, (long)(d.res[i] / SW_WS) * (d.res[i] / SW_WS) * SW_N * SW_N, 1, d.res[i], SW_WS / 2);
+      }
+    }
+    hipLaunchKernelGGL(swin_tables_kernel, dim3((unsigned)((t.total + 255) / 256)), dim3(256), 0, s, t);
+  }
+  // patch embedding: patch operand x Linear (+ bias) -> xb, its LayerNorm -> xa = the residual stream of stage 0
+  RC(vdk_patchify_f32(x, d.B, d.Cin, d.img, d.img, 4, patches, s));
+  RC(gemm32(s, patches, d.Kpe, params + p.pe_w, d.Kpe, xb, d.E, (int)d.T[0], d.E, d.Kpe, params + p.pe_b, nullptr, 0, VDK_ACT_NONE));
+  RC(vdk_layernorm_fwd(xb, d.E, (int)d.T[0], d.E, params + p.pe_nw, params + p.pe_nb, d.eps, xa, d.E, VDK_F32, nullptr, nullptr, s));
+  for (int i = 0; i < d.nst; ++i) {
+    const StageP& sp = p.st[i];
+    const int T = (int)d.T[i], C = d.dim[i], M = 4 * C, H = d.heads[i];
+    const int nW = (d.res[i] / SW_WS) * (d.res[i] / SW_WS);
+    if (i > 0) {      // PatchMerging in front of the stage: gather (xa -> o), LayerNorm (-> h), reduction (-> xa)
+      const int C4 = 4 * d.dim[i - 1];
+      const long n4 = d.T[i - 1] * (d.dim[i - 1] / 4);
+      hipLaunchKernelGGL(swin_merge_kernel<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (const float*)xa, o, d.B, d.res[i - 1], d.dim[i - 1]);
+      RC(vdk_layernorm_fwd(o, C4, T, C4, params + sp.ds_nw, params + sp.ds_nb, d.eps, h, C4, VDK_F32, nullptr, nullptr, s));
+      RC(gemm32(s, h, C4, params + sp.ds_w, C4, xa, C, T, C, C4, nullptr, nullptr, 0, VDK_ACT_NONE));
+    }
+    for (int j = 0; j < d.depth[i]; ++j) {
+      const BlkP& b = sp.blk[j];
+      const bool shifted = (j & 1) && d.res[i] > SW_WS;
+      const VdkWaPrepJob job = {params + b.table, shifted ? (const float*)(base + w.st[i].mask) : nullptr, bm, shifted ? nW : 0, H};
+      RC(vdk_wa_prep_table_batch(&job, 1, s));
+      // x = x + proj(W-MSA(norm1(x)))
+      RC(vdk_layernorm_fwd(xa, C, T, C, params + b.n1w, params + b.n1b, d.eps, h, C, VDK_F32, nullptr, nullptr, s));
+      RC(gemm32(s, h, C, params + b.qkv_w, C, qkv, 3 * C, T, 3 * C, C, params + b.qkv_b, nullptr, 0, VDK_ACT_NONE));
+      RC(vdk_wa_fwd_f32_bm(qkv, 3 * C, o, C, bm, shifted ? nW : 1, (int64_t)(T / SW_N), H, 0.17677669529663687f /* 32^-0.5 */,
+                           (const int32_t*)(base + (shifted ? w.st[i].rowidx3 : w.st[i].rowidx0)), s));
+      RC(gemm32(s, o, C, params + b.proj_w, C, xb, C, T, C, C, params + b.proj_b, xa, C, VDK_ACT_NONE));
+      // x = x + fc2(gelu(fc1(norm2(x))))
+      RC(vdk_layernorm_fwd(xb, C, T, C, params + b.n2w, params + b.n2b, d.eps, h, C, VDK_F32, nullptr, nullptr, s));
+      RC(gemm32(s, h, C, params + b.fc1_w, C, u, M, T, M, C, params + b.fc1_b, nullptr, 0, VDK_ACT_GELU));
+      RC(gemm32(s, u, M, params + b.fc2_w, M, xa, C, T, C, M, params + b.fc2_b, xb, C, VDK_ACT_NONE));
+    }
+  }
+  const int T3 = (int)d.T[d.nst - 1], D = d.dim[d.nst - 1];
+  if (d.C == 0) {
+    RC(vdk_layernorm_fwd(xa, D, T3, D, params + p.norm_w, params + p.norm_b, d.eps, out, D, VDK_F32, nullptr, nullptr, s));
+    return vdk_check_launch("vdk_swin_forward_f32");
+  }
+  float* pooled = (float*)(base + w.pooled);
+  RC(vdk_layernorm_fwd(xa, D, T3, D, params + p.norm_w, params + p.norm_b, d.eps, h, D, VDK_F32, nullptr, nullptr, s));
+  RC(vdk_avgpool_rows_f32_fwd(h, pooled, d.B, T3 / d.B, D, s));
+  RC(gemm32(s, pooled, D, params + p.fc_w, D, out, d.Cp, d.B, d.Cp, D, params + p.fc_b, nullptr, 0, VDK_ACT_NONE));
+  return vdk_check_launch("vdk_swin_forward_f32");
+}
+
+}  // extern "C"

@@ -544,6 +544,8 @@ int vdk_relpos_bias_table_grad(const float* dbias, const int32_t* uses, int32_t 
 // ---- in-library forms for the Swin engine (csrc/swin_engine.hip): the bias tile is prepared ONCE per block and step, straight from the relative-position table, and kept
 // for the backward; d(table) comes from the reduced fragment-order d(bias) in one launch (no un-permute, no [H, 49, 49] tensor in between)
 size_t vdk_wa_bm_bytes(int32_t nW, int32_t H) { return wa_bm_bytes(nW, H); }
+// (the fp32 evaluation kernel of window_attention_f32.hip reads the same tile)
+void vdk_wa_prep_bias(const float* bias, const float* mask, int32_t nW, int32_t H, float* bm, void* stream) { wa_prep(bias, mask, nW, H, bm, (hipStream_t)stream); }
 size_t vdk_wa_bwd_scratch_bytes(int64_t windows, int32_t H) { return (size_t)(wa_bwd_waves(windows, H) + H) * WA_FRAG * 4; }
 int vdk_wa_prep_table_batch(const VdkWaPrepJob* jobs, int n, void* stream) {
   if (n < 0 || (n > 0 && !jobs)) return vdk_fail(VDK_EINVAL, "vdk_wa_prep_table_batch: bad argument");

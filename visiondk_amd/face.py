@@ -247,10 +247,12 @@ class TimmWrapper(nn.Module):
         PyTorch-CPU fp32 embedding to ~1e-6, so downstream cosine top-k lists match the reference's.  Used by FeatureExtractor(precise=True)."""
         be, ol = self.be, self.output_layer
         if not hasattr(self.model, "forward_precise"):
-            raise NotImplementedError("forward_precise (fp32-MFMA evaluation) is built for the ViT and ConvNeXt engines; the Swin backbone evaluates on bf16 operands")
+            raise NotImplementedError("forward_precise (fp32-MFMA evaluation) is built for the native ViT, ConvNeXt and Swin engines; this backbone object has none")
         feat = self.model.forward_precise(x)
         B = x.shape[0]
         if self.is_cnn:
+            # (Swin: feat is the NHWC map [B, 7, 7, C] read as NCHW like the reference's wrapper does, so "channels" = the 7 row indices and h x w = 7 x C; the same
+            # permutation then puts the row index last, vdk_batchnorm1d_fwd takes F = 7, and the Linear's columns follow)
             Cc, HW = feat.shape[1], feat.shape[2] * feat.shape[3]
             rows = feat.permute(0, 2, 3, 1).contiguous().view(B * HW, Cc)
             y, _, _ = ops.batchnorm_fwd(rows, ol[0].weight.detach(), ol[0].bias.detach(), ol[0].running_mean, ol[0].running_var, training=False, eps=ol[0].eps,

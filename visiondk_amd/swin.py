@@ -601,6 +601,28 @@ class SwinEngine:
         be.check(be.lib.vdk_swin_forward(C.byref(cfg), be.ptr(x), be.ptr(self.params), be.ptr(self.wb16), be.ptr(ws), ws.numel(), be.ptr(self._out), be.stream()), "vdk_swin_forward")
         return self._out
 
+    def forward_precise(self, x: torch.Tensor) -> torch.Tensor:
+        """Evaluation forward with every contraction on the fp32 MFMA (vdk_swin_forward_f32, fused fp32 window attention): logits f32 [B, Cp] / map rows f32 [B * 49, 8 E]
+        within ~1e-6 of the reference's PyTorch-CPU fp32 path.  Reads the fp32 master weights, never drops a path, keeps nothing for a backward and has a workspace of its
+        own: the training forward's workspace, factors and serial stay as they are, so it may run between a forward and its backward."""
+        s = self.spec
+        if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (s.in_chans, s.img_size, s.img_size):
+            raise ValueError(f"expected float32 [B, {s.in_chans}, {s.img_size}, {s.img_size}], got {tuple(x.shape)} {x.dtype}")
+        x = x.contiguous()
+        B = x.shape[0]
+        cfg = self._cfg(B)
+        be = self.be
+        need = C.c_size_t(0)
+        be.check(be.lib.vdk_swin_workspace_f32_bytes(C.byref(cfg), C.byref(need)), "vdk_swin_workspace_f32_bytes")
+        if getattr(self, "_ws32", None) is None or self._ws32.numel() < need.value:
+            self._ws32 = None
+            self._ws32 = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        shape = (B, self.cp) if self.cp else (B * self.map_rows, self.features)
+        out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        be.check(be.lib.vdk_swin_forward_f32(C.byref(cfg), be.ptr(x), be.ptr(self.params), be.ptr(self._ws32), self._ws32.numel(), be.ptr(out), be.stream()),
+                 "vdk_swin_forward_f32")
+        return out
+
     def backward(self, dout: torch.Tensor, on_ready=None) -> torch.Tensor:
         """dlogits in the operand format [B, Cp] (feature mode: f32 [B * 49, 8 E]) -> self.grads (flat fp32, overwritten); needs the workspace of the matching forward"""
         from . import _abi
@@ -723,6 +745,7 @@ class SwinTransformer(nn.Module):
             for attr in ("params", "grads", "wb16", "wt16"):
                 setattr(eng, attr, getattr(eng, attr).to(probe.device))
             eng._ws, eng._ws_batch, eng._weights_version = None, -1, None
+            eng._ws32 = None
             for (name, off, numel, shape), (_, p) in zip(eng.entries, self._plist):
                 p.data = eng.params[off:off + numel].view(shape)
         return self
@@ -734,6 +757,17 @@ class SwinTransformer(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return _SwinFunction.apply(x, self, *[p for _, p in self._plist])
+
+    @torch.no_grad()
+    def forward_precise(self, x: torch.Tensor) -> torch.Tensor:
+        """`model(x)` for evaluation with fp32-MFMA contractions (no autograd, no stochastic depth): logits [B, C] or, in feature mode, the NHWC map [B, 7k, 7k, C_last]"""
+        eng = self.engine
+        self._sync_flat()
+        out = eng.forward_precise(x)
+        if eng.cp == 0:
+            r = int(round(eng.map_rows ** 0.5))
+            return out.view(x.shape[0], r, r, eng.features)
+        return out[:, :eng.spec.num_classes]
 
 
 def create_model(name: str, pretrained: bool = False, num_classes: int = 1000, img_size: int = 224, device=None, backend=None, seed: Optional[int] = None,
