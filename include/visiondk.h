@@ -735,6 +735,17 @@ int vdk_margin_stats(const VdkMarginHead* h, const float* cosv, int64_t ldc, int
                      float* stats /* [B][4] */, void* stream);
 int vdk_margin_grad(const VdkMarginHead* h, const float* cosv, int64_t ldc, int32_t B, int32_t Cloc, int64_t c_base, int64_t C_total, const int64_t* labels,
                     const float* gt, const float* gmax, const float* gsum, float label_smoothing, float grad_scale, void* dcos_bf16, int64_t lddc, void* stream);
+/* The statistics and gradient passes of the class-sharded head under GradScaler (`scaler.scale(loss).backward()`, engine/procedure/train.py:205, with the head's columns
+ * split over the ranks): vdk_margin_grad_amp writes dcos16 [B, lddc] (dc_dtype = VDK_BF16 | VDK_F16; columns Cloc .. lddc - 1 zeroed, rows >= B the caller's to zero) =
+ * loss_scale[0] * grad_scale * dLoss/dcos with the scale read from DEVICE memory (NULL: 1); the statistics -- and with them the loss -- are never scaled.  Both passes
+ * evaluate plain ArcFace once per row (the target's logit and jacobian, on the shard that owns the target column; VDK_MARGIN_GENERIC=1 selects the per-entry evaluation,
+ * bit-identical) and share one exponential, so use them as a pair: stats [B][4] from vdk_margin_stats_amp, gmax / gsum [B] merged from them, as for vdk_margin_stats /
+ * vdk_margin_grad, which keep their own kernels. */
+int vdk_margin_stats_amp(const VdkMarginHead* h, const float* cosv, int64_t ldc, int32_t B, int32_t Cloc, int64_t c_base, const int64_t* labels, const float* gt,
+                         float* stats /* [B][4] */, void* stream);
+int vdk_margin_grad_amp(const VdkMarginHead* h, const float* cosv, int64_t ldc, int32_t B, int32_t Cloc, int64_t c_base, int64_t C_total, const int64_t* labels,
+                        const float* gt, const float* gmax, const float* gsum, float label_smoothing, float grad_scale, const float* loss_scale, void* dcos16, int64_t lddc,
+                        int32_t dc_dtype, void* stream);
 int vdk_margin_bwd(const VdkMarginHead* h, const float* cosv, int64_t ldc, int32_t B, int32_t C, const int64_t* labels, const float* dlogits,
                    int64_t lddl, void* dcos_bf16, int64_t lddc, void* stream);
 

@@ -405,6 +405,116 @@ __global__ __launch_bounds__(256) void margin_grad_kernel(MarginP P, const float
   }
   for (int c = C4 + tid; c < (int)lddc; c += 256) dr[c] = f2bf(c < Cloc ? grad(cr[c], c) : 0.f);
 }
+// The sharded passes under GradScaler and with the fused kernel's economies (vdk_margin_stats_amp / vdk_margin_grad_amp; the two kernels above stay what they were,
+// bit for bit, behind the old entry points).  Both use vexp, in every instantiation, so that statistics and gradient see the same exponentials and the ARC form equals the
+// generic one bit for bit.  ARC (ArcFace without per-row margins): the margin function is evaluated once per row, on the shard that owns the target column; on every other
+// shard no entry takes the target branch and lg_t / jc_t are never selected.  The row context (MV-Softmax) comes from the all-reduced gt[row] in both forms.
+template <bool ARC>
+struct ShardRow {
+  MarginP P; RowCtx R; int yt; float lg_t, jc_t;
+  __device__ __forceinline__ ShardRow(const MarginP& P0, int row, const float* cr, int Cloc, long c_base, const long long* y, const float* gt) : P(P0) {
+    margin_row_params(P, row);
+    const long t = (long)y[row] - c_base;              // local target column, -1 when it lies outside this shard (32-bit compares in the loops)
+    yt = (t >= 0 && t < Cloc) ? (int)t : -1;
+    R = margin_row_ctx(P, gt[row]);
+    lg_t = 0.f; jc_t = 0.f;
+    if (ARC && yt >= 0) margin_eval(P, R, cr[yt], true, lg_t, jc_t);
+  }
+  __device__ __forceinline__ void ev(float cv, bool tg, float& lg, float& jc) const {
+    if (ARC) {
+      const float c = fminf(fmaxf(cv, -1.0f), 1.0f);
+      lg = tg ? lg_t : P.s * c;
+      jc = tg ? jc_t : (c == cv ? P.s : 0.0f);          // s * (1 inside the clamp's range, 0 outside)
+    } else margin_eval(P, R, cv, tg, lg, jc);
+  }
+};
+template <bool ARC>
+__global__ __launch_bounds__(256) void margin_stats_amp_kernel(MarginP P0, const float* __restrict__ cosv, long ldc, int Cloc, long c_base, const long long* __restrict__ y,
+                                                               const float* __restrict__ gt, float* __restrict__ stats) {
+  __shared__ float red[4];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* cr = cosv + (long)row * ldc;
+  const ShardRow<ARC> S(P0, row, cr, Cloc, c_base, y, gt);
+  const int yt = S.yt;
+  float m = -3.0e38f, se = 0.f, sm = 0.f, tl = 0.f;
+  auto visit = [&](float cv, int c) {
+    float lg, jc; S.ev(cv, c == yt, lg, jc);
+    sm += lg;
+    if (c == yt) tl = lg;
+    if (lg > m) { se *= vexp(m - lg); m = lg; }
+    se += vexp(lg - m);
+  };
+  auto visit4 = [&](const f32x4& cv, int c) {
+    float lg[4], jc;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { S.ev(cv[e], c + e == yt, lg[e], jc); if (c + e == yt) tl = lg[e]; }
+    sm += (lg[0] + lg[1]) + (lg[2] + lg[3]);
+    const float m4 = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
+    if (m4 > m) { se *= vexp(m - m4); m = m4; }
+    se += (vexp(lg[0] - m) + vexp(lg[1] - m)) + (vexp(lg[2] - m) + vexp(lg[3] - m));
+  };
+  // 16-byte loads, MCE_U in flight per thread (see margin_ce_vec_kernel); scalar loop for unaligned blocks and the tail
+  const int C4 = (((ldc & 3) == 0) && (((size_t)cosv & 15) == 0)) ? (Cloc & ~3) : 0;
+  for (int base = tid * 4; base < C4; base += 256 * 4 * MCE_U) {
+    f32x4 v[MCE_U];
+#pragma unroll
+    for (int u = 0; u < MCE_U; ++u) { const int c = base + u * 1024; if (c < C4) v[u] = *(const f32x4*)(cr + c); }
+#pragma unroll
+    for (int u = 0; u < MCE_U; ++u) {
+      const int c = base + u * 1024;
+      if (c < C4) visit4(v[u], c);
+    }
+  }
+  for (int c = C4 + tid; c < Cloc; c += 256) visit(cr[c], c);
+  const float mx = block_max<4>(m, red);
+  se = block_sum<4>(se * vexp(m - mx), red);
+  sm = block_sum<4>(sm, red);
+  tl = block_sum<4>(tl, red);
+  if (tid == 0) { float* o = stats + (long)row * 4; o[0] = mx; o[1] = se; o[2] = sm; o[3] = tl; }
+}
+// OF: format of dcos (bf16 | fp16).  lscale: GradScaler's loss scale on the device, multiplied into gscale (NULL: 1); only dcos carries it.
+// SHARD_OPAQUE: the gradient leaves `grad` as a finished fp32 value.  Left to itself the compiler folds the last multiply into the fp16 conversion (v_fma_mixlo_f16: one
+// rounding) at some call sites and not at others (v_mul_f32 + v_cvt_pk_f16_f32: two), so the 16-byte path, the scalar path and the two instantiations would differ in
+// the last fp16 bit now and then; a shard's dcos must not depend on where its column block starts.
+#ifdef VDK_EMU
+#define SHARD_OPAQUE(x) ((void)0)
+#else
+#define SHARD_OPAQUE(x) asm("" : "+v"(x))
+#endif
+template <bool ARC, int OF>
+__global__ __launch_bounds__(256) void margin_grad_amp_kernel(MarginP P0, const float* __restrict__ cosv, long ldc, int Cloc, long c_base, long C_total,
+                                                              const long long* __restrict__ y, const float* __restrict__ gt, const float* __restrict__ gmax,
+                                                              const float* __restrict__ gsum, float label_smoothing, float gscale, const float* __restrict__ lscale,
+                                                              bf16_t* __restrict__ dcos, long lddc) {
+  if (lscale) gscale *= lscale[0];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* cr = cosv + (long)row * ldc;
+  const ShardRow<ARC> S(P0, row, cr, Cloc, c_base, y, gt);
+  const int yt = S.yt;
+  const float mx = gmax[row], inv = 1.0f / gsum[row], epsc = label_smoothing / (float)C_total;
+  auto grad = [&](float cv, int c) -> float {
+    float lg, jc; S.ev(cv, c == yt, lg, jc);
+    float g = vexp(lg - mx) * inv - epsc;
+    if (c == yt) g -= (1.0f - label_smoothing);
+    g = g * gscale * jc;
+    if (OF == VDK_OPF_F16) SHARD_OPAQUE(g);
+    return g;
+  };
+  bf16_t* dr = dcos + (long)row * lddc;
+  const bool al = ((ldc & 3) == 0) && (((size_t)cosv & 15) == 0) && ((lddc & 3) == 0) && (((size_t)dcos & 7) == 0);
+  const int C4 = al ? (Cloc & ~3) : 0;
+  for (int base = tid * 4; base < C4; base += 256 * 4 * MCE_U) {
+    f32x4 v[MCE_U];
+#pragma unroll
+    for (int u = 0; u < MCE_U; ++u) { const int c = base + u * 1024; if (c < C4) v[u] = *(const f32x4*)(cr + c); }
+#pragma unroll
+    for (int u = 0; u < MCE_U; ++u) {
+      const int c = base + u * 1024;
+      if (c < C4) *(u32x2*)(dr + c) = (u32x2){pack_op2<OF>(grad(v[u][0], c), grad(v[u][1], c + 1)), pack_op2<OF>(grad(v[u][2], c + 2), grad(v[u][3], c + 3))};
+    }
+  }
+  for (int c = C4 + tid; c < (int)lddc; c += 256) dr[c] = f2op<OF>(c < Cloc ? grad(cr[c], c) : 0.f);
+}
 
 // backward of the logits-returning form: dcos = dlogits * jac (bf16, padded columns zeroed)
 __global__ __launch_bounds__(256) void margin_bwd_kernel(MarginP P, const float* __restrict__ cosv, long ldc, int C, const long long* __restrict__ y,
@@ -581,6 +691,35 @@ int vdk_margin_grad(const VdkMarginHead* h, const float* cosv, int64_t ldc, int3
   hipLaunchKernelGGL(margin_grad_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, P, cosv, (long)ldc, (int)Cloc, (long)c_base, (long)C_total,
                      (const long long*)labels, gt, gmax, gsum, label_smoothing, grad_scale, (bf16_t*)dcos_bf16, (long)lddc);
   return vdk_check_launch("vdk_margin_grad");
+}
+// ArcFace without per-row margins takes the once-per-row evaluation unless VDK_MARGIN_GENERIC=1 (A/B and tests; read per call, as in vdk_margin_ce_amp)
+static bool shard_arc_path(const MarginP& P) {
+  const char* genv = getenv("VDK_MARGIN_GENERIC");
+  return P.mode == VDK_HEAD_ARCFACE && !P.row_margin && !(genv && atoi(genv) == 1);
+}
+int vdk_margin_stats_amp(const VdkMarginHead* h, const float* cosv, int64_t ldc, int32_t B, int32_t Cloc, int64_t c_base, const int64_t* labels, const float* gt,
+                         float* stats, void* stream) {
+  MarginP P; int rc = fill_params(h, &P); if (rc) return rc;
+  if (!cosv || !labels || !gt || !stats || B <= 0 || Cloc <= 0 || ldc < Cloc) return vdk_fail(VDK_EINVAL, "vdk_margin_stats_amp: bad argument");
+#define MSA(ARC) hipLaunchKernelGGL((margin_stats_amp_kernel<ARC>), dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, P, cosv, (long)ldc, (int)Cloc, (long)c_base, \
+                                    (const long long*)labels, gt, stats)
+  if (shard_arc_path(P)) MSA(true); else MSA(false);
+#undef MSA
+  return vdk_check_launch("vdk_margin_stats_amp");
+}
+int vdk_margin_grad_amp(const VdkMarginHead* h, const float* cosv, int64_t ldc, int32_t B, int32_t Cloc, int64_t c_base, int64_t C_total, const int64_t* labels,
+                        const float* gt, const float* gmax, const float* gsum, float label_smoothing, float grad_scale, const float* loss_scale, void* dcos16, int64_t lddc,
+                        int32_t dc_dtype, void* stream) {
+  MarginP P; int rc = fill_params(h, &P); if (rc) return rc;
+  if (!cosv || !labels || !gt || !gmax || !gsum || !dcos16 || B <= 0 || Cloc <= 0 || C_total < Cloc || ldc < Cloc || lddc < Cloc || (dc_dtype != VDK_BF16 && dc_dtype != VDK_F16))
+    return vdk_fail(VDK_EINVAL, "vdk_margin_grad_amp: bad argument (dc_dtype VDK_BF16 | VDK_F16)");
+  const bool f16 = dc_dtype == VDK_F16;
+#define MGA(ARC, OF) hipLaunchKernelGGL((margin_grad_amp_kernel<ARC, OF>), dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, P, cosv, (long)ldc, (int)Cloc, (long)c_base, \
+                                        (long)C_total, (const long long*)labels, gt, gmax, gsum, label_smoothing, grad_scale, loss_scale, (bf16_t*)dcos16, (long)lddc)
+  if (shard_arc_path(P)) { if (f16) MGA(true, VDK_OPF_F16); else MGA(true, 0); }
+  else { if (f16) MGA(false, VDK_OPF_F16); else MGA(false, 0); }
+#undef MGA
+  return vdk_check_launch("vdk_margin_grad_amp");
 }
 int vdk_margin_bwd(const VdkMarginHead* h, const float* cosv, int64_t ldc, int32_t B, int32_t C, const int64_t* labels, const float* dlogits,
                    int64_t lddl, void* dcos_bf16, int64_t lddc, void* stream) {

@@ -448,7 +448,9 @@ class FaceTrainStep:
         cos_planes: 3 = fp32-class cosines in the head (split-bf16 planes: the reference's CPU path), 1 = single bf16 operands (the reference's GPU path: the head runs
         under autocast, train.py:118).  shard_head (with comm): every rank keeps the columns [rank * C / world, (rank + 1) * C / world) of the margin head, trains them with
         `heads.sharded_margin_ce` (features all-gathered, per-row softmax statistics and the [B, D] feature gradient all-reduced) and never all-reduces the
-        [D, C] head gradient (2 GB at C = 10^6).  `gather_head()` writes the shards back into `head.weight` for evaluation / checkpoints.
+        [D, C] head gradient (2 GB at C = 10^6).  `gather_head()` writes the shards back into `head.weight` for evaluation / checkpoints.  Over an fp16
+        backbone the sharded head runs the step's arithmetic -- fp16 planes (cos_planes applies), d(loss)/d(cos) in fp16 carrying the loss scale -- and the ranks skip an
+        overflowing step together; over a bf16 backbone it keeps its three bf16 planes.
         layer_wise: the second entry of the yaml's `optimizer` list (cbir.yaml:113): two parameter groups, backbone + neck at lr and the
         margin head at 10 x lr (built/layer_optimizer.py:26-29); `param_groups[1]['lr']` is then the head's rate and a scheduler drives both.
         comm: visiondk_amd.comm.GradAllReduce for data parallelism (one process per GPU): parameters and BatchNorm buffers are broadcast from
@@ -471,9 +473,6 @@ class FaceTrainStep:
             raise ValueError("an fp16 backbone engine under a TimmWrapper built with operand='bf16': build the wrapper with operand='fp16' (its neck follows the format)")
         if self.amp and precision == "fp32":
             raise ValueError("precision='fp32' runs fp32 activations: build the backbone with operand='bf16' (its 16-bit copies are not used in that mode)")
-        if self.amp and shard_head and comm is not None and comm.active:      # (an inactive communicator -- one rank -- never shards: nothing to refuse)
-            raise NotImplementedError("the class-sharded head is built for bf16 operands (its three passes take no loss scale yet): build the backbone with "
-                                      "operand='bf16' -- `backbone: {timm-...: {operand: bf16}}` in the config -- when shard_head=True is used across ranks")
         if precision == "fp32" and not hasattr(self.bb.model.engine, "precision"):
             raise NotImplementedError("precision='fp32' is built for the ConvNeXt backbones of the face / CBIR task (the engine with an fp32-class training mode)")
         self.precision = precision
@@ -570,8 +569,10 @@ class FaceTrainStep:
         fn = _NeckCNNFn if bb.is_cnn else _NeckFn
         emb = fn.apply(feat, ol[0].weight, ol[0].bias, ol[2].weight, ol[2].bias, ol[3].weight, ol[3].bias, bb)
         if self.shard_head:
+            # (bf16: the arguments of always -- three bf16 planes, no loss scale; fp16: the replicated head's arithmetic, with the scale multiplied into d(loss)/d(cos))
+            amp_kw = dict(cos_planes=self.cos_planes, operand="fp16", loss_scale=self.loss_state) if self.amp else {}
             self.loss_rows, demb, dW = heads.sharded_margin_ce(self.head, emb.detach(), y, self.hs, self.c0, self.head.weight.shape[1], group=self.comm.group,
-                                                              label_smoothing=self.label_smoothing)
+                                                              label_smoothing=self.label_smoothing, **amp_kw)
         else:
             self.loss_rows, demb, dW = self.head.margin_ce(emb.detach(), y, self.label_smoothing, cos_planes=self.cos_planes, precise=self.precision == "fp32",
                                                            operand="fp16" if self.amp else "bf16", loss_scale=self.loss_state if self.amp else None)
@@ -603,7 +604,8 @@ class FaceTrainStep:
         self._sumsq(eng.grads)
         for p in self.small:
             self._sumsq(p.grad.contiguous())
-        if self.shard_head:                                            # the head's share of the global gradient norm: sum over the shards
+        if self.shard_head:                                            # the head's share of the global gradient norm: sum over the shards (an inf / NaN in one shard's
+                                                                       # scaled gradient reaches every rank's _nsq here: the ranks skip the step together)
             import torch.distributed as dist
             be.check(be.lib.vdk_sumsq_f32(be.ptr(dW), dW.numel(), be.ptr(self._nsq_head), be.ptr(self._ws), self._ws.numel(), be.stream()), "vdk_sumsq_f32")
             dist.all_reduce(self._nsq_head, op=dist.ReduceOp.SUM, group=self.comm.group)

@@ -304,15 +304,25 @@ class HeadFactory:
 
 
 def sharded_margin_ce(head: _MarginHead, feats: torch.Tensor, labels: torch.Tensor, weight_shard: torch.Tensor, c_base: int, num_class: int, group=None,
-                      label_smoothing: float = 0.0, grad_scale: Optional[float] = None):
+                      label_smoothing: float = 0.0, grad_scale: Optional[float] = None, cos_planes: int = 3, operand: str = "bf16",
+                      loss_scale: Optional[torch.Tensor] = None):
     """Class-sharded form of `head.margin_ce` for data-parallel training with many identities: this rank holds the weight columns
     [c_base, c_base + weight_shard.shape[1]) of the [D, num_class] head.  Features and labels of ALL ranks are all-gathered (B_total x D floats), every rank
     scores them against its shard, three small all-reduces ([B_total] target cosine, [B_total] max, [B_total, 3] sums) give the global softmax statistics,
     and the feature gradient is summed over the shards ([B_total, D]).  The [D, C] head gradient never crosses a link: each rank gets the gradient of its own
     shard.  Returns (loss_rows of the LOCAL samples, dfeats of the local samples, dweight of the shard); grad_scale defaults to 1 / B_local, the scale
-    `margin_ce` uses, so that the optimizer's 1 / world factor applies to both forms alike."""
+    `margin_ce` uses, so that the optimizer's 1 / world factor applies to both forms alike.
+    cos_planes / operand / loss_scale as in `margin_ce`: operand = "fp16" multiplies fp16 planes and writes an fp16 d(loss)/d(cos); loss_scale (a device scalar, e.g.
+    `FaceTrainStep.loss_state`) is multiplied into d(loss)/d(cos), so dfeats and dweight come back SCALED and the optimizer pass un-scales; the loss rows are never scaled.
+    A non-finite scaled gradient on any shard reaches every rank through the all-reduced dfeats and, in FaceTrainStep, through the all-reduced norm of the shards'
+    gradients, so the ranks skip in lockstep.  operand = "bf16" without a loss scale runs vdk_margin_stats / vdk_margin_grad (per-entry evaluation, expf) and returns what
+    it always returned; every other combination runs vdk_margin_stats_amp / vdk_margin_grad_amp (ArcFace evaluated once per row, v_exp_f32)."""
     import torch.distributed as dist
     be = head.be
+    if operand not in ("bf16", "fp16"):
+        raise ValueError("operand must be 'bf16' or 'fp16'")
+    dt16 = torch.float16 if operand == "fp16" else torch.bfloat16
+    amp = operand == "fp16" or loss_scale is not None
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     B, D = feats.shape
@@ -323,14 +333,18 @@ def sharded_margin_ce(head: _MarginHead, feats: torch.Tensor, labels: torch.Tens
     else:
         fall, lall = feats.contiguous(), labels.contiguous()
     Bt, Cloc = fall.shape[0], weight_shard.shape[1]
-    st = _forward_cos(be, fall, weight_shard.detach())
+    st = _forward_cos(be, fall, weight_shard.detach(), cos_planes, dtype=dt16)
     dev = feats.device
     gt = torch.empty(Bt, dtype=torch.float32, device=dev)
     be.check(be.lib.vdk_margin_target_cos(be.ptr(st.cos), st.Cp, Bt, Cloc, c_base, be.ptr(lall), be.ptr(gt), be.stream()), "vdk_margin_target_cos")
     if world > 1:
         dist.all_reduce(gt, op=dist.ReduceOp.SUM, group=group)
     stats = torch.empty((Bt, 4), dtype=torch.float32, device=dev)
-    be.check(be.lib.vdk_margin_stats(C.byref(head.cfg), be.ptr(st.cos), st.Cp, Bt, Cloc, c_base, be.ptr(lall), be.ptr(gt), be.ptr(stats), be.stream()), "vdk_margin_stats")
+    if amp:
+        be.check(be.lib.vdk_margin_stats_amp(C.byref(head.cfg), be.ptr(st.cos), st.Cp, Bt, Cloc, c_base, be.ptr(lall), be.ptr(gt), be.ptr(stats), be.stream()),
+                 "vdk_margin_stats_amp")
+    else:
+        be.check(be.lib.vdk_margin_stats(C.byref(head.cfg), be.ptr(st.cos), st.Cp, Bt, Cloc, c_base, be.ptr(lall), be.ptr(gt), be.ptr(stats), be.stream()), "vdk_margin_stats")
     gmax = stats[:, 0].contiguous()
     if world > 1:
         dist.all_reduce(gmax, op=dist.ReduceOp.MAX, group=group)
@@ -339,10 +353,18 @@ def sharded_margin_ce(head: _MarginHead, feats: torch.Tensor, labels: torch.Tens
         dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
     gsum = sums[:, 0].contiguous()
     loss_all = gmax + torch.log(gsum) - (1.0 - label_smoothing) * sums[:, 2] - label_smoothing * sums[:, 1] / num_class
-    dcos = torch.zeros((st.Bp, st.Cp), dtype=torch.bfloat16, device=dev)
     gs = 1.0 / B if grad_scale is None else grad_scale
-    be.check(be.lib.vdk_margin_grad(C.byref(head.cfg), be.ptr(st.cos), st.Cp, Bt, Cloc, c_base, num_class, be.ptr(lall), be.ptr(gt), be.ptr(gmax), be.ptr(gsum),
-                                    label_smoothing, gs, be.ptr(dcos), st.Cp, be.stream()), "vdk_margin_grad")
+    if amp:
+        dcos = torch.empty((st.Bp, st.Cp), dtype=dt16, device=dev)      # rows < Bt are written whole (padding columns zeroed) by the kernel
+        if st.Bp > Bt:
+            dcos[Bt:].zero_()
+        be.check(be.lib.vdk_margin_grad_amp(C.byref(head.cfg), be.ptr(st.cos), st.Cp, Bt, Cloc, c_base, num_class, be.ptr(lall), be.ptr(gt), be.ptr(gmax), be.ptr(gsum),
+                                            label_smoothing, gs, be.ptr(loss_scale), be.ptr(dcos), st.Cp, _abi.F16_ if operand == "fp16" else _abi.BF16, be.stream()),
+                 "vdk_margin_grad_amp")
+    else:
+        dcos = torch.zeros((st.Bp, st.Cp), dtype=torch.bfloat16, device=dev)
+        be.check(be.lib.vdk_margin_grad(C.byref(head.cfg), be.ptr(st.cos), st.Cp, Bt, Cloc, c_base, num_class, be.ptr(lall), be.ptr(gt), be.ptr(gmax), be.ptr(gsum),
+                                        label_smoothing, gs, be.ptr(dcos), st.Cp, be.stream()), "vdk_margin_grad")
     df_all, dW = _backward_from_dcos(be, st, weight_shard.detach(), dcos)      # df of every sample w.r.t. THIS shard's columns
     if world > 1:
         dist.all_reduce(df_all, op=dist.ReduceOp.SUM, group=group)
