@@ -12,6 +12,9 @@
 //                                     refreshed by vdk_sgd_step); wt16 = per-Linear [in, out] bf16 copies for dgrad.
 //   residual stream                 : fp32 [B*N, D] per block boundary (what timm keeps in fp32 under autocast)
 //   GEMM operands / saved tensors   : bf16
+//
+// Classifier mode computes the last block's tail (everything behind its attention) on the class-token rows only, see cls_tail_on().  The switch VDK_VIT_CLS_TAIL
+// decides which rows the forward saves and which the backward reads: it must not change between a forward and its backward.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -297,6 +300,14 @@ static int vit_plan(const VitDims& d, WsPlan* w) {
 
 #define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
+// Class-token tail: the classifier head reads token 0 of every image (global_pool='token'), so behind the LAST block's attention only the B class rows are needed --
+// proj + residual, norm2, the MLP and their backward run on B rows instead of B * N (row b * N of a [T, D] tensor = the same pointer with pitch N * D).  Needs a head,
+// a class token and 16-bit operands (the fp8 GEMMs want M >= 256).  VDK_VIT_CLS_TAIL=0 keeps the full path; read per call (the tests flip it in-process).
+static bool cls_tail_on(const VitDims& d) {
+  const char* e = getenv("VDK_VIT_CLS_TAIL");
+  return d.C > 0 && d.cls && !d.fp8 && !(e && e[0] == '0');
+}
+
 // ---- fp8 mode (VdkVitConfig.fp8): OCP e4m3 / e5m2 operands for the forward and input-gradient GEMMs of the block Linears ------------------------------------
 struct F8 {
   int mode; unsigned char* w8; unsigned char* wt8; float* amax; float* sc; float* si; unsigned char* a8; unsigned char* a8b;
@@ -491,6 +502,7 @@ int vdk_vit_forward(const VdkVitConfig* cfg, const float* x, const float* params
 
   const float scale = 0.125f;  // head_dim ** -0.5, head_dim == 64
   F8 f8; RC(f8_init(cfg, d, p, &f8, (unsigned char*)(base + w.a8), (unsigned char*)(base + w.a8b)));
+  const bool cls_tail = cls_tail_on(d);
   for (int l = 0; l < d.L; ++l) {
     const PLayout::Blk& b = p.blk[l];
     float* xin = X + (size_t)(2 * l) * XS; float* xmid = xin + XS; float* xout = xmid + XS;
@@ -517,11 +529,16 @@ int vdk_vit_forward(const VdkVitConfig* cfg, const float* x, const float* params
     RC(vdk_layernorm_fwd(xin, D, T, D, params + b.n1w, params + b.n1b, d.eps, h1, D, DT16, mean1, rstd1, s));
     RC(gemm(s, h1, D, wb + b.qkv_w, D, qkv, 3 * D, T, 3 * D, D, DT16, params + b.qkv_b, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
     RC(vdk_attention_fwd_dt(qkv, 3 * D, o, D, lse, d.B, d.N, d.H, 64, scale, DT16, s));
-    RC(gemm(s, o, D, wb + b.proj_w, D, xmid, D, T, D, D, VDK_F32, params + b.proj_b, xin, D, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
+    // class-token tail (last block of a classifier): from here on only row b * N of every image is computed.  The fp32 stream tensors keep those rows where they lie
+    // (pitch N * D); h2, g, u hold them packed in their first B rows.  mean2 / rstd2 hold B entries.
+    const bool tail = cls_tail && l == d.L - 1;
+    const int R = tail ? d.B : T;
+    const int64_t ldt = tail ? (int64_t)d.N * D : D;
+    RC(gemm(s, o, ldt, wb + b.proj_w, D, xmid, ldt, R, D, D, VDK_F32, params + b.proj_b, xin, ldt, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
     // x = x + fc2(gelu(fc1(norm2(x))))
-    RC(vdk_layernorm_fwd(xmid, D, T, D, params + b.n2w, params + b.n2b, d.eps, h2, D, DT16, mean2, rstd2, s));
-    RC(gemm(s, h2, D, wb + b.fc1_w, D, g, M, T, M, D, DT16, params + b.fc1_b, nullptr, 0, ACT_FC1, u, M, 1, 0, nullptr, 0));
-    RC(gemm(s, g, M, wb + b.fc2_w, M, xout, D, T, D, M, VDK_F32, params + b.fc2_b, xmid, D, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
+    RC(vdk_layernorm_fwd(xmid, ldt, R, D, params + b.n2w, params + b.n2b, d.eps, h2, D, DT16, mean2, rstd2, s));
+    RC(gemm(s, h2, D, wb + b.fc1_w, D, g, M, R, M, D, DT16, params + b.fc1_b, nullptr, 0, ACT_FC1, u, M, 1, 0, nullptr, 0));
+    RC(gemm(s, g, M, wb + b.fc2_w, M, xout, ldt, R, D, M, VDK_F32, params + b.fc2_b, xmid, ldt, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
   }
   float* xl = X + (size_t)(2 * d.L) * XS;
   float* meanf = stats + (size_t)d.L * 4 * T; float* rstdf = meanf + T;
@@ -635,6 +652,7 @@ int vdk_vit_backward(const VdkVitConfig* cfg, const void* dlogits, const float* 
   const size_t EV_SIDE_DONE = 8;   // slots [8, 8 + L + 2): side stream finished layer l (index l + 1; 0 = embeddings)
   size_t ev_p = EV_SIDE_DONE + d.L + 4;   // producer events, a fresh slot per use
   RC(ev_order(0, s, s2));           // the side stream starts after whatever precedes this call on the main stream
+  const bool cls_tail = cls_tail_on(d);
 
   // ---- head + final norm -------------------------------------------------------------------------
   bool last_fc2_bias_done = false;   // fc2.bias gradient of block l is produced with DXAB(l): by the final norm's backward (l = L-1) or by block l+1's norm1 backward
@@ -651,7 +669,8 @@ int vdk_vit_backward(const VdkVitConfig* cfg, const void* dlogits, const float* 
     RC(linear_wgrad(s, d, w, base, dl, d.Cp, hf, D, d.B, d.Bp, d.Cp, D, grads + p.head_w, grads + p.head_b, 0));
     bf16_t* dhf = (bf16_t*)(base + w.dhf);
     RC(gemm(s, dl, d.Cp, wt + p.headT, d.Cp, dhf, D, d.B, D, d.Cp, DT16, nullptr, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
-    if (hipMemsetAsync(dxa, 0, XS * 4, s) != hipSuccess || hipMemsetAsync(DXAB(d.L - 1), 0, XS * 2, s) != hipSuccess)
+    // full path: every row of dL/dx_out but the class rows is zero.  Class-token tail: the last block reads the class rows only, nothing to fill here
+    if (!cls_tail && (hipMemsetAsync(dxa, 0, XS * 4, s) != hipSuccess || hipMemsetAsync(DXAB(d.L - 1), 0, XS * 2, s) != hipSuccess))
       return vdk_fail(VDK_ELAUNCH, "vdk_vit_backward: memset failed");
     float* xl = X + (size_t)(2 * d.L) * XS;
     float* meanf = stats + (size_t)d.L * 4 * T; float* rstdf = meanf + T;
@@ -685,6 +704,21 @@ int vdk_vit_backward(const VdkVitConfig* cfg, const void* dlogits, const float* 
     const bool one_stream = (s2 == s);
     VdkReduceJob jobs[8]; int nj = 0;          // this block's small reductions (LayerNorm dgamma | dbeta, Linear bias gradients): one launch at its end
     char* const lnws0 = base + w.lnws; char* const lnws1 = lnws0 + w.lnws_bytes;
+    const bool ocs_ln = one_stream && D <= 1024;
+    // fp16 operands: the residual-gradient stream travels in 16 bits.  Every norm backward writes dL/dx twice -- fp32 for the next norm backward's residual term, 16-bit
+    // for the next GEMM -- and reads the fp32 one back: 310 of its 620 MB per launch at ViT-B/16 (the kernel streams at HBM rate, so bytes are its time).  With g16 the
+    // 16-bit copy is the stream: the sum is formed in fp32 registers and rounded once per norm (24 roundings of 2^-11 down the trunk; measured against the fp32 oracle
+    // in tests/test_fp16_operands.py and bench.py's parity block, bound 5e-3 on every gradient).  bf16 (8 mantissa bits) keeps the fp32 stream.
+    static const bool g16_on = !(getenv("VDK_VIT_G16") && atoi(getenv("VDK_VIT_G16")) == 0);
+    const bool g16 = g16_on && ocs_ln && !f8.mode && t_opf == VDK_OPF_F16 && D > 512 && D <= 1024;
+    // Class-token tail (see cls_tail_on): down to the proj weight gradient this block works on the B class rows, R rows of pitch ldt; du, h2, g, u hold them packed.
+    // What the full-size kernels below read whole is zero outside those rows: dO (dsm, attention backward) and the dL/dx_mid that the norm1 backward adds (dxmb where the
+    // 16-bit copy is the stream, else the fp32 dxm).  dsm's class rows carry dh2 first, then dO, like the whole tensor does on the full path.
+    const bool tail = cls_tail && l == d.L - 1;
+    const int R = tail ? d.B : T, Rp = tail ? d.Bp : d.Tp;
+    const int64_t ldt = tail ? (int64_t)d.N * D : D;
+    if (tail && (hipMemsetAsync(dsm, 0, XS * 2, s) != hipSuccess || (g16 ? hipMemsetAsync(dxmb, 0, XS * 2, s) : hipMemsetAsync(dxm, 0, XS * 4, s)) != hipSuccess))
+      return vdk_fail(VDK_ELAUNCH, "vdk_vit_backward: memset failed");
     // MLP branch: dxa / dxab hold dL/dx_out
     RC(ev_order(ev_p++, s, s2));
     if (f8.mode) {
@@ -708,36 +742,29 @@ int vdk_vit_backward(const VdkVitConfig* cfg, const void* dlogits, const float* 
       // (dGELU epilogue below), proj.bias with dxmb (norm2 backward below); only qkv.bias still comes from the A tiles of the dh1 GEMM (dqkv is attention's output).
       int fx = 0;
       const bool have_fc2b = (l == d.L - 1) ? last_fc2_bias_done : fc2_bias_from_norm1;
-      RC(dgrad_with_bias(s, w, base, dxab, D, wt + p.blkT[l].fc2, D, du, M, T, M, D, ACT_DFC2, u, M, have_fc2b ? nullptr : grads + b.fc2_b, &fz, 0, jobs, &nj,
+      RC(dgrad_with_bias(s, w, base, dxab, ldt, wt + p.blkT[l].fc2, D, du, M, R, M, D, ACT_DFC2, u, M, have_fc2b ? nullptr : grads + b.fc2_b, &fz, 0, jobs, &nj,
                          grads + b.fc1_b, &fx, 1));   // du
-      RC(linear_wgrad(s2, d, w, base, dxab, D, g, M, T, d.Tp, D, M, grads + b.fc2_w, (fz || have_fc2b) ? nullptr : grads + b.fc2_b, 0));
+      RC(linear_wgrad(s2, d, w, base, dxab, ldt, g, M, R, Rp, D, M, grads + b.fc2_w, (fz || have_fc2b) ? nullptr : grads + b.fc2_b, 0));
       if (fx) {
-        RC(gemm(s, du, M, wt + p.blkT[l].fc1, M, dsm, D, T, D, M, DT16, nullptr, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));   // dh2
+        RC(gemm(s, du, M, wt + p.blkT[l].fc1, M, dsm, ldt, R, D, M, DT16, nullptr, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));   // dh2
         fz = 1;
       } else {
-        RC(dgrad_with_bias(s, w, base, du, M, wt + p.blkT[l].fc1, M, dsm, D, T, D, M, VDK_ACT_NONE, nullptr, 0, grads + b.fc1_b, &fz, 1, jobs, &nj));   // dh2
+        RC(dgrad_with_bias(s, w, base, du, M, wt + p.blkT[l].fc1, M, dsm, ldt, R, D, M, VDK_ACT_NONE, nullptr, 0, grads + b.fc1_b, &fz, 1, jobs, &nj));   // dh2
       }
-      RC(linear_wgrad(s2, d, w, base, du, M, h2, D, T, d.Tp, M, D, grads + b.fc1_w, fz ? nullptr : grads + b.fc1_b, 0));
+      RC(linear_wgrad(s2, d, w, base, du, M, h2, D, R, Rp, M, D, grads + b.fc1_w, fz ? nullptr : grads + b.fc1_b, 0));
     } else {
-      RC(linear_wgrad(s2, d, w, base, dxab, D, g, M, T, d.Tp, D, M, grads + b.fc2_w, grads + b.fc2_b, 0));
-      RC(gemm(s, dxab, D, wt + p.blkT[l].fc2, D, du, M, T, M, D, DT16, nullptr, nullptr, 0, ACT_DFC2, u, M, 1, 0, nullptr, 0));   // du
+      RC(linear_wgrad(s2, d, w, base, dxab, ldt, g, M, R, Rp, D, M, grads + b.fc2_w, grads + b.fc2_b, 0));
+      RC(gemm(s, dxab, ldt, wt + p.blkT[l].fc2, D, du, M, R, M, D, DT16, nullptr, nullptr, 0, ACT_DFC2, u, M, 1, 0, nullptr, 0));   // du
       RC(ev_order(ev_p++, s, s2));
-      RC(linear_wgrad(s2, d, w, base, du, M, h2, D, T, d.Tp, M, D, grads + b.fc1_w, grads + b.fc1_b, 0));
-      RC(gemm(s, du, M, wt + p.blkT[l].fc1, M, dsm, D, T, D, M, DT16, nullptr, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));   // dh2
+      RC(linear_wgrad(s2, d, w, base, du, M, h2, D, R, Rp, M, D, grads + b.fc1_w, grads + b.fc1_b, 0));
+      RC(gemm(s, du, M, wt + p.blkT[l].fc1, M, dsm, ldt, R, D, M, DT16, nullptr, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));   // dh2
     }
-    const bool ocs_ln = one_stream && D <= 1024;
-    // fp16 operands: the residual-gradient stream travels in 16 bits.  Every norm backward writes dL/dx twice -- fp32 for the next norm backward's residual term, 16-bit
-    // for the next GEMM -- and reads the fp32 one back: 310 of its 620 MB per launch at ViT-B/16 (the kernel streams at HBM rate, so bytes are its time).  With g16 the
-    // 16-bit copy is the stream: the sum is formed in fp32 registers and rounded once per norm (24 roundings of 2^-11 down the trunk; measured against the fp32 oracle
-    // in tests/test_fp16_operands.py and bench.py's parity block, bound 5e-3 on every gradient).  bf16 (8 mantissa bits) keeps the fp32 stream.
-    static const bool g16_on = !(getenv("VDK_VIT_G16") && atoi(getenv("VDK_VIT_G16")) == 0);
-    const bool g16 = g16_on && ocs_ln && !f8.mode && t_opf == VDK_OPF_F16 && D > 512 && D <= 1024;
     const bool lq = f8.mode && f8_fused(f8) && ocs_ln;               // the norm backward kernels write the e5m2 copies of dxmb / DXAB(l - 1) into the operand scratch
     const LnQ8 q8m = {f8.a8, (long)D, f8.sc + 12 * l + 10, f8.amax + 12 * l + 10, 1};
-    if (g16) RC(vdk_layernorm_bwd_deferred(dsm, D, DT16, xmid, D, mean2, rstd2, params + b.n2w, nullptr, D, T, D, nullptr, D, dxmb, D, grads + b.n2w, grads + b.n2b, lnws0,
+    if (g16) RC(vdk_layernorm_bwd_deferred(dsm, ldt, DT16, xmid, ldt, mean2, rstd2, params + b.n2w, nullptr, ldt, R, D, nullptr, ldt, dxmb, ldt, grads + b.n2w, grads + b.n2b, lnws0,
                                            w.lnws_bytes, s, &jobs[nj], grads + b.proj_b, &jobs[nj + 1], nullptr, 0, nullptr, nullptr, 1, dxab));
     else
-    RC(vdk_layernorm_bwd_deferred(dsm, D, DT16, xmid, D, mean2, rstd2, params + b.n2w, dxa, D, T, D, dxm, D, dxmb, D, grads + b.n2w, grads + b.n2b, lnws0,
+    RC(vdk_layernorm_bwd_deferred(dsm, ldt, DT16, xmid, ldt, mean2, rstd2, params + b.n2w, dxa, ldt, R, D, dxm, ldt, dxmb, ldt, grads + b.n2w, grads + b.n2b, lnws0,
                                   w.lnws_bytes, s, &jobs[nj], ocs_ln ? grads + b.proj_b : nullptr, ocs_ln ? &jobs[nj + 1] : nullptr, lq ? &q8m : nullptr));
     nj += ocs_ln ? 2 : 1;
     // attention branch: dxm / dxmb hold dL/dx_mid
@@ -746,14 +773,14 @@ int vdk_vit_backward(const VdkVitConfig* cfg, const void* dlogits, const float* 
       RC(gemm8(s, f8, dxmb, 12 * l + 10, 1, f8.wt8 + p.blkT[l].proj, 12 * l + 5, D, dsm, D, T, D, D, VDK_BF16, nullptr, nullptr, 0, VDK_ACT_NONE, nullptr, 0, lq ? f8.a8 : nullptr));   // do
       RC(linear_wgrad(s2, d, w, base, dxmb, D, o, D, T, d.Tp, D, D, grads + b.proj_w, ocs_ln ? nullptr : grads + b.proj_b, 0));
     } else if (one_stream && ocs_ln) {
-      RC(gemm(s, dxmb, D, wt + p.blkT[l].proj, D, dsm, D, T, D, D, DT16, nullptr, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));   // do
-      RC(linear_wgrad(s2, d, w, base, dxmb, D, o, D, T, d.Tp, D, D, grads + b.proj_w, nullptr, 0));
+      RC(gemm(s, dxmb, ldt, wt + p.blkT[l].proj, D, dsm, ldt, R, D, D, DT16, nullptr, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));   // do
+      RC(linear_wgrad(s2, d, w, base, dxmb, ldt, o, ldt, R, Rp, D, D, grads + b.proj_w, nullptr, 0));
     } else if (one_stream) {
-      RC(dgrad_with_bias(s, w, base, dxmb, D, wt + p.blkT[l].proj, D, dsm, D, T, D, D, VDK_ACT_NONE, nullptr, 0, grads + b.proj_b, &fz, 2, jobs, &nj));   // do
-      RC(linear_wgrad(s2, d, w, base, dxmb, D, o, D, T, d.Tp, D, D, grads + b.proj_w, fz ? nullptr : grads + b.proj_b, 0));
+      RC(dgrad_with_bias(s, w, base, dxmb, ldt, wt + p.blkT[l].proj, D, dsm, ldt, R, D, D, VDK_ACT_NONE, nullptr, 0, grads + b.proj_b, &fz, 2, jobs, &nj));   // do
+      RC(linear_wgrad(s2, d, w, base, dxmb, ldt, o, ldt, R, Rp, D, D, grads + b.proj_w, fz ? nullptr : grads + b.proj_b, 0));
     } else {
-      RC(linear_wgrad(s2, d, w, base, dxmb, D, o, D, T, d.Tp, D, D, grads + b.proj_w, grads + b.proj_b, 0));
-      RC(gemm(s, dxmb, D, wt + p.blkT[l].proj, D, dsm, D, T, D, D, DT16, nullptr, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));   // do
+      RC(linear_wgrad(s2, d, w, base, dxmb, ldt, o, ldt, R, Rp, D, D, grads + b.proj_w, grads + b.proj_b, 0));
+      RC(gemm(s, dxmb, ldt, wt + p.blkT[l].proj, D, dsm, ldt, R, D, D, DT16, nullptr, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));   // do
     }
     // dqkv; with the one-pass small-N kernel the qkv.bias gradient's per-image partials (column sums of the dq | dk | dv rows it stores) come out of the same launch
     // (round 5: the separate pass over dqkv was 13 x 42 us per ViT-B/16 step); VDK_VIT_QKVB_ATTN=0 keeps that pass
