@@ -195,12 +195,12 @@ int vdk_transpose_bf16(const void* in, int64_t ldi, int32_t R, int32_t C, void* 
  * routing, -1 hands the choice back to the VDK_ATTN_LEGACY environment variable. */
 
 /* timm Attention core: softmax(q k^T * scale) v per head, flash-style (the N x N matrix is never
- * written).  qkv: bf16 [B, N, 3, H, 64] = the fused qkv Linear output (row stride ld elements);
- * o: bf16 [B, N, H*64] (row stride ldo); lse: f32 [B, H, N] log-sum-exp saved for backward (NULL ok).
- * head_dim must be 64 (ViT-B/16: 12 heads, ViT-L: 16 heads). */
+ * written).  qkv: bf16 [B, N, 3, H, hd] = the fused qkv Linear output (row stride ld elements);
+ * o: bf16 [B, N, H*hd] (row stride ldo); lse: f32 [B, H, N] log-sum-exp saved for backward (NULL ok).
+ * hd = head_dim must be 64 (ViT-B/16: 12 heads, ViT-L: 16 heads) or 80 (ViT-H/14: 16 heads; csrc/attention_hd.hip); anything else: VDK_EUNSUPPORTED. */
 int vdk_attention_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, int32_t B, int32_t N, int32_t H,
                       int32_t head_dim, float scale, void* stream);
-/* backward: dqkv bf16 [B, N, 3, H, 64] (row stride lddqkv); dvec: f32 scratch [B, H, N]. */
+/* backward: dqkv bf16 [B, N, 3, H, hd] (row stride lddqkv); dvec: f32 scratch [B, H, N]. */
 int vdk_attention_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, void* dqkv,
                       int64_t lddqkv, float* dvec, int32_t B, int32_t N, int32_t H, int32_t head_dim, float scale, void* stream);
 /* vdk_attention_fwd / vdk_attention_bwd with the 16-bit format of q, k, v, o, dO, dqkv as a parameter: dtype = VDK_BF16 | VDK_F16.  VDK_F16 is the arithmetic of the

@@ -1,0 +1,56 @@
+"""The head-dim-80 attention kernels (csrc/attention_hd.hip) read and write nothing outside their operands' extents: the raw ABI on guard-banded operands with padded
+pitches, as tests/test_extent_isolation.py does for the 64-wide kernels (I1 guards intact, I2 outputs bit-identical across the fill patterns, I3 the same bits as the
+contiguous call), plus the accuracy check of tests/test_attention_hd80.py so that a result that is wrong in the same way in every run cannot pass."""
+import pytest
+import torch
+
+from tests.extent import run_isolated
+from tests.test_attention import _ref, _rel
+from tests.test_attention_hd80 import errors_vs_torch
+
+BF, HF, F32 = torch.bfloat16, torch.float16, torch.float32
+DT = {BF: 0, HF: 2}
+HD = 80
+
+
+def p(t):
+    return t.data_ptr()
+
+
+@pytest.mark.parametrize("dtype", [BF, HF], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("B,N,H", [(2, 17, 2), (1, 257, 1), (2, 100, 3)])
+def test_attention_hd80_extents(be, dev, B, N, H, dtype):
+    """B = H = 1: what lies beyond N is the guard; B * H > 1: it is another item's (or another head's) live data"""
+    D = H * HD
+    scale = HD ** -0.5
+    torch.manual_seed(30)
+    qkv0 = (torch.randn(B * N, 3 * D) * 1.5).to(dtype); qkv0[N // 2, :D] *= 4.0
+    dout0 = torch.randn(B * N, D).to(dtype)
+
+    def case(ar):
+        # ld = 3 D + 8 and ldo = D + 24 shift the 16-byte row starts from row to row (the header asks for ld % 8 only); lddqkv = 3 D + 64 keeps them aligned
+        qkv = ar.put(qkv0, 8, "qkv"); dout = ar.put(dout0, 24, "dout")
+        o = ar.out((B * N, D), dtype, 24, "o"); lse = ar.out(B * H * N, F32, 0, "lse"); dqkv = ar.out((B * N, 3 * D), dtype, 64, "dqkv"); dvec = ar.out(B * H * N, F32, 0, "dvec")
+        ldo = o.stride(0)                                                # (o and dout share ldo in the ABI: both are padded by 24)
+        be.check(be.lib.vdk_attention_fwd_dt(p(qkv), qkv.stride(0), p(o), ldo, p(lse), B, N, H, HD, scale, DT[dtype], be.stream()), "attention fwd")
+        be.check(be.lib.vdk_attention_bwd_dt(p(qkv), qkv.stride(0), p(o), p(dout), ldo, p(lse), p(dqkv), dqkv.stride(0), p(dvec), B, N, H, HD, scale, DT[dtype], be.stream()),
+                 "attention bwd")
+        return {"o": o, "lse": lse, "dqkv": dqkv}
+
+    got, _ = run_isolated(case, dev, sync=torch.cuda.synchronize if be.device_only else None)
+    e = errors_vs_torch(qkv0.reshape(B, N, 3 * D), dout0.reshape(B, N, D), H, got["o"].cpu().reshape(B, N, D), got["lse"].cpu().reshape(B, H, N),
+                        got["dqkv"].cpu().reshape(B, N, 3 * D))
+    print(f"hd80 extents {dtype} B{B} N{N} H{H}: " + " ".join(f"{k}={v:.3e}" for k, v in e.items()))
+    assert e["lse"] < 1e-5
+    if dtype == BF:
+        assert e["o"] < 6e-3                                             # the bounds of tests/test_attention.py
+    else:                                                                # fp16 forward: against the 64-wide kernels at the same (B, N, H) and seed, as in tests/test_attention_hd80.py
+        from visiondk_amd import ops
+        torch.manual_seed(30)
+        q64 = (torch.randn(B, N, 3 * H * 64) * 1.5).to(dtype); q64[0, N // 2, :H * 64] *= 4.0
+        o64, _ = ops.attention_fwd(q64.to(dev), H, backend=be)
+        e64 = _rel(o64.float().cpu(), _ref(q64.float(), H)[0])
+        print(f"hd64 o={e64:.3e}")
+        assert e["o"] <= 1.5 * e64
+    for name in ("dq", "dk", "dv"):
+        assert e[name] < (1.5e-2 if dtype == BF else 2e-3), name

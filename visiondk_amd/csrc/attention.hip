@@ -384,6 +384,10 @@ int vdk_attention_small_bwd(const void* qkv, int64_t ld, const void* o, const vo
                             int32_t H, float scale, int opf, void* stream);
 // long sequences (attention_long.hip): K / V streamed through a double-buffered LDS chunk by LDS-DMA, online softmax
 int vdk_attention_long_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, int32_t B, int32_t N, int32_t H, float scale, int opf, void* stream);
+// attention_hd.hip: the streaming kernels for head_dim 80 (every N; not touched by vdk_attention_force_legacy or the VDK_ATTN_* routing switches)
+int vdk_attention_hd_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, int32_t B, int32_t N, int32_t H, int32_t head_dim, float scale, int opf, void* stream);
+int vdk_attention_hd_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, void* dqkv, int64_t ldd, float* dvec, int32_t B, int32_t N,
+                         int32_t H, int32_t head_dim, float scale, int opf, void* stream);
 int vdk_attention_long_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, void* dqkv, int64_t ldd, float* dvec, int32_t B, int32_t N,
                            int32_t H, float scale, int opf, void* stream);
 static thread_local int g_attn_legacy = -1;   // -1: env VDK_ATTN_LEGACY decides; 0 / 1: forced by vdk_attention_force_legacy (A/B benchmarking, tests of the long-sequence kernels at small N)
@@ -410,7 +414,7 @@ int vdk_attention_fwd_dt(const void*, int64_t, void*, int64_t, float*, int32_t, 
 int vdk_attention_bwd_dt(const void*, int64_t, const void*, const void*, int64_t, const float*, void*, int64_t, float*, int32_t, int32_t, int32_t, int32_t, float, int32_t, void*);
 int vdk_attention_force_legacy(int32_t on) { g_attn_legacy = on < 0 ? -1 : (on ? 1 : 0); return VDK_OK; }
 
-// qkv: bf16 [B, N, 3, H, 64] (timm's fused qkv Linear output, row stride ld = 3*H*64); o: bf16 [B, N, H*64];
+// qkv: bf16 [B, N, 3, H, hd] (timm's fused qkv Linear output, row stride ld >= 3*H*hd); o: bf16 [B, N, H*hd]; hd = head_dim: 64 or 80;
 // lse: f32 [B, H, N] (saved for backward; may be NULL for inference).
 int vdk_attention_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, int32_t B, int32_t N, int32_t H,
                       int32_t head_dim, float scale, void* stream) {
@@ -422,7 +426,12 @@ int vdk_attention_fwd_dt(const void* qkv, int64_t ld, void* o, int64_t ldo, floa
                          int32_t head_dim, float scale, int32_t dtype, void* stream) {
   if (!qkv || !o || B <= 0 || N <= 0 || H <= 0 || (dtype != VDK_BF16 && dtype != VDK_F16)) return vdk_fail(VDK_EINVAL, "vdk_attention_fwd: bad argument");
   const int opf = dtype == VDK_F16 ? VDK_OPF_F16 : VDK_OPF_BF16;
-  if (head_dim != A_HD) return vdk_fail(VDK_EUNSUPPORTED, "vdk_attention_fwd: head_dim must be 64");
+  if (head_dim == 80) {
+    if ((ld & 7) || (ldo & 7)) return vdk_fail(VDK_EINVAL, "vdk_attention_fwd: ld % 8");
+    const int rc = vdk_attention_hd_fwd(qkv, ld, o, ldo, lse, B, N, H, head_dim, scale, opf, stream);
+    return rc ? rc : vdk_check_launch("vdk_attention_fwd");
+  }
+  if (head_dim != A_HD) return vdk_fail(VDK_EUNSUPPORTED, "vdk_attention_fwd: head_dim must be 64 or 80");
   if ((ld & 7) || (ldo & 7)) return vdk_fail(VDK_EINVAL, "vdk_attention_fwd: ld % 8");
   if (N <= 256 && N < attn_long_min() && !attn_legacy()) {
     const int rc = vdk_attention_small_fwd(qkv, ld, o, ldo, lse, B, N, H, scale, opf, stream);
@@ -444,9 +453,10 @@ int vdk_attention_fwd_dt(const void* qkv, int64_t ld, void* o, int64_t ldo, floa
   return vdk_check_launch("vdk_attention_fwd");
 }
 
-// dqkv: bf16 [B, N, 3, H, 64] like qkv.  dvec: f32 scratch [B, H, N].
+// dqkv: bf16 [B, N, 3, H, hd] like qkv.  dvec: f32 scratch [B, H, N].
 // the same backward with the qkv.bias gradient's partials as a by-product where the chosen kernel can deliver them (the one-pass small-N form): cspart f32 [B][3 * H * 64]
-// = per image the column sums of its dq | dk | dv rows as stored; *produced = 1 when written (the caller reduces over B), 0 otherwise (the caller sums dqkv itself)
+// = per image the column sums of its dq | dk | dv rows as stored; *produced = 1 when written (the caller reduces over B), 0 otherwise (the caller sums dqkv itself;
+// always so at head_dim 80)
 int vdk_attention_bwd_cs(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, void* dqkv, int64_t lddqkv, float* dvec, int32_t B, int32_t N,
                          int32_t H, int32_t head_dim, float scale, int32_t dtype, float* cspart, int32_t* produced, void* stream_) {
   vdk_attention_small_want_colsum(cspart);
@@ -464,7 +474,12 @@ int vdk_attention_bwd_dt(const void* qkv, int64_t ld, const void* o, const void*
   hipStream_t stream = (hipStream_t)stream_;
   if (!qkv || !o || !dout || !lse || !dqkv || !dvec || B <= 0 || N <= 0 || H <= 0 || (dtype != VDK_BF16 && dtype != VDK_F16)) return vdk_fail(VDK_EINVAL, "vdk_attention_bwd: bad argument");
   const int opf = dtype == VDK_F16 ? VDK_OPF_F16 : VDK_OPF_BF16;
-  if (head_dim != A_HD) return vdk_fail(VDK_EUNSUPPORTED, "vdk_attention_bwd: head_dim must be 64");
+  if (head_dim == 80) {
+    if ((ld & 7) || (ldo & 7) || (lddqkv & 7)) return vdk_fail(VDK_EINVAL, "vdk_attention_bwd: ld % 8");
+    const int rc = vdk_attention_hd_bwd(qkv, ld, o, dout, ldo, lse, dqkv, lddqkv, dvec, B, N, H, head_dim, scale, opf, stream_);
+    return rc ? rc : vdk_check_launch("vdk_attention_bwd");
+  }
+  if (head_dim != A_HD) return vdk_fail(VDK_EUNSUPPORTED, "vdk_attention_bwd: head_dim must be 64 or 80");
   if ((ld & 7) || (ldo & 7) || (lddqkv & 7)) return vdk_fail(VDK_EINVAL, "vdk_attention_bwd: ld % 8");
   if (N <= 224 && N < attn_long_min() && !attn_legacy()) {
     const int rc = vdk_attention_small_bwd(qkv, ld, o, dout, ldo, lse, dqkv, lddqkv, dvec, B, N, H, scale, opf, stream_);

@@ -73,8 +73,8 @@ static bool gelu_saved_grad() {
 static inline int64_t up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
 struct VitDims {
-  int B, img, ps, Cin, D, L, H, M, C, Cp, np, N, T, Kraw, Kpe, Tp, Bp, cls, pre /* VdkVitConfig.pre_norm */, fp8, opf /* operand format: VDK_OPF_BF16 | VDK_OPF_F16 (VdkVitConfig.operand) */;   // cls: 1 = class token in row 0 of every image's token block   // Kraw = in_chans * patch^2, Kpe = Kraw padded to 8 (patch 14: 588 -> 592)
-  float eps;
+  int B, img, ps, Cin, D, L, H, M, C, Cp, np, N, T, Kraw, Kpe, Tp, Bp, cls, pre /* VdkVitConfig.pre_norm */, hd /* head dim: 64 or 80 */, fp8, opf /* operand format: VDK_OPF_BF16 | VDK_OPF_F16 (VdkVitConfig.operand) */;   // cls: 1 = class token in row 0 of every image's token block   // Kraw = in_chans * patch^2, Kpe = Kraw padded to 8 (patch 14: 588 -> 592)
+  float eps, scale /* hd ** -0.5 */;
 };
 static int vit_dims(const VdkVitConfig* c, VitDims* d) {
   if (!c) return vdk_fail(VDK_EINVAL, "vit: null config");
@@ -82,7 +82,9 @@ static int vit_dims(const VdkVitConfig* c, VitDims* d) {
   d->H = c->heads; d->M = c->mlp_dim; d->C = c->num_classes; d->eps = c->ln_eps;
   if (d->B <= 0 || d->img <= 0 || d->ps <= 0 || d->img % d->ps || d->Cin <= 0 || d->D <= 0 || d->L <= 0 || d->H <= 0 || d->M <= 0 || d->C < 0)
     return vdk_fail(VDK_EINVAL, "vit: bad config value");
-  if (d->D != d->H * 64) return vdk_fail(VDK_EUNSUPPORTED, "vit: head_dim must be 64 (dim == 64 * heads)");
+  if (d->D != d->H * 64 && d->D != d->H * 80) return vdk_fail(VDK_EUNSUPPORTED, "vit: head_dim must be 64 or 80 (dim == 64 * heads or 80 * heads)");
+  d->hd = d->D / d->H;
+  d->scale = 1.0f / sqrtf((float)d->hd);
   if ((d->D & 7) || (d->M & 7)) return vdk_fail(VDK_EUNSUPPORTED, "vit: dim and mlp_dim must be multiples of 8");
   d->Kraw = d->Cin * d->ps * d->ps;
   d->Kpe = (int)up(d->Kraw, 8);     // patch 14 (timm vit_*_patch14_*: K = 588): the GEMM operands are zero-padded copies, the parameter itself stays [D, Kraw]
@@ -500,7 +502,7 @@ int vdk_vit_forward(const VdkVitConfig* cfg, const float* x, const float* params
     RC(vdk_layernorm_fwd(X0, D, T, D, params + p.npre_w, params + p.npre_b, d.eps, X, D, VDK_F32, ps, ps + T, s));
   }
 
-  const float scale = 0.125f;  // head_dim ** -0.5, head_dim == 64
+  const float scale = d.scale;  // head_dim ** -0.5
   F8 f8; RC(f8_init(cfg, d, p, &f8, (unsigned char*)(base + w.a8), (unsigned char*)(base + w.a8b)));
   const bool cls_tail = cls_tail_on(d);
   for (int l = 0; l < d.L; ++l) {
@@ -518,7 +520,7 @@ int vdk_vit_forward(const VdkVitConfig* cfg, const float* x, const float* params
       if (fl) RC(vdk_layernorm_fwd_q8(xin, D, T, D, params + b.n1w, params + b.n1b, d.eps, h1, D, mean1, rstd1, f8.a8, D, 0, f8.sc + sl + 0, f8.amax + sl + 0, s));
       else RC(vdk_layernorm_fwd(xin, D, T, D, params + b.n1w, params + b.n1b, d.eps, h1, D, VDK_BF16, mean1, rstd1, s));
       RC(gemm8(s, f8, h1, sl + 0, 0, f8.w8 + b.qkv_w, sl + 4, D, qkv, 3 * D, T, 3 * D, D, VDK_BF16, params + b.qkv_b, nullptr, 0, VDK_ACT_NONE, nullptr, 0, fl ? f8.a8 : nullptr));
-      RC(vdk_attention_fwd(qkv, 3 * D, o, D, lse, d.B, d.N, d.H, 64, scale, s));
+      RC(vdk_attention_fwd(qkv, 3 * D, o, D, lse, d.B, d.N, d.H, d.hd, scale, s));
       RC(gemm8(s, f8, o, sl + 1, 0, f8.w8 + b.proj_w, sl + 5, D, xmid, D, T, D, D, VDK_F32, params + b.proj_b, xin, D, VDK_ACT_NONE, nullptr, 0));
       if (fl) RC(vdk_layernorm_fwd_q8(xmid, D, T, D, params + b.n2w, params + b.n2b, d.eps, h2, D, mean2, rstd2, f8.a8, D, 0, f8.sc + sl + 2, f8.amax + sl + 2, s));
       else RC(vdk_layernorm_fwd(xmid, D, T, D, params + b.n2w, params + b.n2b, d.eps, h2, D, VDK_BF16, mean2, rstd2, s));
@@ -528,7 +530,7 @@ int vdk_vit_forward(const VdkVitConfig* cfg, const float* x, const float* params
     }
     RC(vdk_layernorm_fwd(xin, D, T, D, params + b.n1w, params + b.n1b, d.eps, h1, D, DT16, mean1, rstd1, s));
     RC(gemm(s, h1, D, wb + b.qkv_w, D, qkv, 3 * D, T, 3 * D, D, DT16, params + b.qkv_b, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
-    RC(vdk_attention_fwd_dt(qkv, 3 * D, o, D, lse, d.B, d.N, d.H, 64, scale, DT16, s));
+    RC(vdk_attention_fwd_dt(qkv, 3 * D, o, D, lse, d.B, d.N, d.H, d.hd, scale, DT16, s));
     // class-token tail (last block of a classifier): from here on only row b * N of every image is computed.  The fp32 stream tensors keep those rows where they lie
     // (pitch N * D); h2, g, u hold them packed in their first B rows.  mean2 / rstd2 hold B entries.
     const bool tail = cls_tail && l == d.L - 1;
@@ -788,7 +790,7 @@ int vdk_vit_backward(const VdkVitConfig* cfg, const void* dlogits, const float* 
     {
       static const bool fuse_on = !(getenv("VDK_VIT_QKVB_ATTN") && atoi(getenv("VDK_VIT_QKVB_ATTN")) == 0);
       float* csp = (fuse_on && !f8.mode && one_stream && (size_t)d.B * 3 * D * 4 <= w.csws_bytes) ? (float*)(base + w.csws + (size_t)3 * w.csws_bytes) : nullptr;
-      RC(vdk_attention_bwd_cs(qkv, 3 * D, o, dsm, D, lse, dqkv, 3 * D, dvec, d.B, d.N, d.H, 64, 0.125f, DT16, csp, &qkvb_done, s));
+      RC(vdk_attention_bwd_cs(qkv, 3 * D, o, dsm, D, lse, dqkv, 3 * D, dvec, d.B, d.N, d.H, d.hd, d.scale, DT16, csp, &qkvb_done, s));
       if (qkvb_done) { jobs[nj] = VdkReduceJob{csp, (long)3 * D, d.B, (long)3 * D, grads + b.qkv_b, 1.0f}; ++nj; }
     }
     RC(ev_order(ev_p++, s, s2));
@@ -913,7 +915,10 @@ int vdk_vit_workspace_f32_bytes(const VdkVitConfig* cfg, size_t* bytes) {
 int vdk_vit_forward_f32(const VdkVitConfig* cfg, const float* x, const float* params, void* ws, size_t ws_bytes, float* logits, void* stream_) {
   hipStream_t s = (hipStream_t)stream_;
   VitDims d; RC(vit_dims(cfg, &d));
-  if (d.Kraw != d.Kpe) return vdk_fail(VDK_EUNSUPPORTED, "vdk_vit_forward_f32: in_chans*patch*patch must be a multiple of 8 on the fp32 path");
+  // The stem GEMM reads the patch rows and the [D, Kraw] master weight as they lie: vdk_gemm_f32_nt needs K % 4 only (patch 14: 588).  The head-dim-80 models
+  // (ViT-H/14) are served on that rule; at head dim 64 the older K % 8 refusal stands unchanged (tests/test_vit.py pins it for the patch-14 ids there).
+  if (d.Kraw & 3) return vdk_fail(VDK_EUNSUPPORTED, "vdk_vit_forward_f32: in_chans*patch*patch must be a multiple of 4 on the fp32 path");
+  if (d.hd == 64 && d.Kraw != d.Kpe) return vdk_fail(VDK_EUNSUPPORTED, "vdk_vit_forward_f32: in_chans*patch*patch must be a multiple of 8 on the fp32 path");
   PLayout p; RC(vit_layout(d, &p));
   WsF32 w; vit_plan_f32(d, &w);
   if (!x || !params || !ws || !logits) return vdk_fail(VDK_EINVAL, "vdk_vit_forward_f32: null pointer");
@@ -929,9 +934,9 @@ int vdk_vit_forward_f32(const VdkVitConfig* cfg, const float* x, const float* pa
   RC(vdk_patchify_f32(x, d.B, d.Cin, d.img, d.img, d.ps, patches, s));
   {
     VdkGemmF32Desc g = {};
-    g.A = patches; g.lda = d.Kpe; g.B = params + p.pe_w; g.ldb = d.Kpe; g.C = xa + (size_t)d.cls * D; g.ldc = D; g.M = d.np; g.N = D; g.K = d.Kpe;
+    g.A = patches; g.lda = d.Kraw; g.B = params + p.pe_w; g.ldb = d.Kraw; g.C = xa + (size_t)d.cls * D; g.ldc = D; g.M = d.np; g.N = D; g.K = d.Kraw;
     g.bias = params + p.pe_b; g.residual = params + p.pos + (size_t)d.cls * D; g.ldr = D; g.alpha = 1.0f;
-    g.batch1 = d.B; g.batch2 = 1; g.sa1 = (int64_t)d.np * d.Kpe; g.sc1 = (int64_t)N * D;
+    g.batch1 = d.B; g.batch2 = 1; g.sa1 = (int64_t)d.np * d.Kraw; g.sc1 = (int64_t)N * D;
     if (d.B > 65535) return vdk_fail(VDK_EUNSUPPORTED, "vdk_vit_forward_f32: batch <= 65535");
     RC(vdk_gemm_f32_nt(&g, s));
   }
@@ -946,13 +951,13 @@ int vdk_vit_forward_f32(const VdkVitConfig* cfg, const float* x, const float* pa
     RC(gemm32(s, h, D, params + b.qkv_w, D, qkv, 3 * D, T, 3 * D, D, params + b.qkv_b, nullptr, 0, VDK_ACT_NONE));
     {   // S[b, head] = Q K^T (scale applied inside the softmax), then P = softmax(S / 8), then O = P V
       VdkGemmF32Desc g = {};
-      g.A = qkv; g.lda = 3 * D; g.B = qkv + D; g.ldb = 3 * D; g.C = S; g.ldc = Np; g.M = N; g.N = N; g.K = 64; g.alpha = 1.0f;
-      g.batch1 = d.B; g.batch2 = d.H; g.sa1 = (int64_t)N * 3 * D; g.sa2 = 64; g.sb1 = g.sa1; g.sb2 = 64; g.sc1 = (int64_t)d.H * N * Np; g.sc2 = (int64_t)N * Np;
+      g.A = qkv; g.lda = 3 * D; g.B = qkv + D; g.ldb = 3 * D; g.C = S; g.ldc = Np; g.M = N; g.N = N; g.K = d.hd; g.alpha = 1.0f;
+      g.batch1 = d.B; g.batch2 = d.H; g.sa1 = (int64_t)N * 3 * D; g.sa2 = d.hd; g.sb1 = g.sa1; g.sb2 = d.hd; g.sc1 = (int64_t)d.H * N * Np; g.sc2 = (int64_t)N * Np;
       RC(vdk_gemm_f32_nt(&g, s));
-      RC(vdk_softmax_rows_f32(S, Np, (int64_t)d.B * d.H * N, N, 0.125f, s));
+      RC(vdk_softmax_rows_f32(S, Np, (int64_t)d.B * d.H * N, N, d.scale, s));
       VdkGemmF32Desc v = {};
-      v.A = S; v.lda = Np; v.B = qkv + 2 * D; v.ldb = 3 * D; v.b_kmajor = 1; v.C = o; v.ldc = D; v.M = N; v.N = 64; v.K = Np; v.alpha = 1.0f;
-      v.batch1 = d.B; v.batch2 = d.H; v.sa1 = g.sc1; v.sa2 = g.sc2; v.sb1 = (int64_t)N * 3 * D; v.sb2 = 64; v.sc1 = (int64_t)N * D; v.sc2 = 64;
+      v.A = S; v.lda = Np; v.B = qkv + 2 * D; v.ldb = 3 * D; v.b_kmajor = 1; v.C = o; v.ldc = D; v.M = N; v.N = d.hd; v.K = Np; v.alpha = 1.0f;
+      v.batch1 = d.B; v.batch2 = d.H; v.sa1 = g.sc1; v.sa2 = g.sc2; v.sb1 = (int64_t)N * 3 * D; v.sb2 = d.hd; v.sc1 = (int64_t)N * D; v.sc2 = d.hd;
       RC(vdk_gemm_f32_nt(&v, s));
     }
     RC(gemm32(s, o, D, params + b.proj_w, D, xb, D, T, D, D, params + b.proj_b, xa, D, VDK_ACT_NONE));

@@ -180,7 +180,7 @@ def _ws(be, fn, *args, device):
 
 
 def attention_fwd(qkv: torch.Tensor, heads: int, scale: Optional[float] = None, backend=None):
-    """qkv bf16 [B, N, 3*heads*64] -> (o bf16 [B, N, heads*64], lse f32 [B, heads, N])."""
+    """qkv bf16 / fp16 [B, N, 3*heads*hd] -> (o [B, N, heads*hd], lse f32 [B, heads, N]); hd = 64 or 80 (any other head dim: VDK_EUNSUPPORTED)."""
     be = _be(backend)
     B, N, three_d = qkv.shape
     D = three_d // 3

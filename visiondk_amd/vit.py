@@ -39,7 +39,7 @@ class VitSpec:
     pre_norm: bool = False        # timm pre_norm=True (the CLIP ViTs): LayerNorm `norm_pre` in front of the blocks, patch embedding without a bias
 
 
-# timm 0.9.16 model ids the engine covers (head_dim 64; patch 14 works through zero-padded operand copies of the patch-embedding weight)
+# timm 0.9.16 model ids the engine covers (head_dim 64, or 80 for ViT-H/14: csrc/attention_hd.hip; patch 14 works through zero-padded operand copies of the patch-embedding weight)
 TIMM_VITS = {
     "vit_tiny_patch16_224": dict(dim=192, depth=12, heads=3, mlp_dim=768),
     "vit_small_patch16_224": dict(dim=384, depth=12, heads=6, mlp_dim=1536),
@@ -56,6 +56,8 @@ TIMM_VITS = {
     "vit_base_patch16_clip_224": dict(dim=768, depth=12, heads=12, mlp_dim=3072, pre_norm=True, ln_eps=1e-5),
     "vit_large_patch14_clip_224": dict(dim=1024, depth=24, heads=16, mlp_dim=4096, patch_size=14, pre_norm=True, ln_eps=1e-5),
     "vit_large_patch14_clip_336": dict(dim=1024, depth=24, heads=16, mlp_dim=4096, patch_size=14, img_size=336, pre_norm=True, ln_eps=1e-5),
+    # ViT-H/14 CLIP (`vit_huge_patch14_clip_224.laion2b_ft_in12k_in1k` in the shipped YAMLs): head_dim 1280 / 16 = 80
+    "vit_huge_patch14_clip_224": dict(dim=1280, depth=32, heads=16, mlp_dim=5120, patch_size=14, pre_norm=True, ln_eps=1e-5),
     # class_token=False + global_pool='map' (SigLIP): served by VisionTransformerMap
     "vit_base_patch16_siglip_224": dict(dim=768, depth=12, heads=12, mlp_dim=3072, class_token=False),
     "vit_large_patch16_siglip_256": dict(dim=1024, depth=24, heads=16, mlp_dim=4096, img_size=256, class_token=False),
