@@ -25,6 +25,12 @@ int vdk_gemm_debug_stamps(void* device_u64_buffer);
 int vdk_attention_force_legacy(int32_t on);
 /* tests: one job of the batched row reduction (vdk_reduce_rows_batch) */
 int vdk_debug_reduce_rows_job(float* buf, int64_t ld, int32_t S, int64_t n, float* out, float scale, void* stream);
+/* tests: the class-query attention kernels of csrc/attention_cls.hip on their own (the ViT engine reaches them in-library).  Tensors as for vdk_attention_fwd_dt /
+ * vdk_attention_bwd_dt, but only row b * N of q, o, dout, dq and lse[(b * H + h) * N] are touched; cspart: f32 [B][3 * H * head_dim] or NULL; grid: workgroups, 0 = default */
+int vdk_debug_attention_cls_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, int32_t B, int32_t N, int32_t H, int32_t head_dim, float scale, int32_t dtype,
+                                int32_t grid, void* stream);
+int vdk_debug_attention_cls_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, void* dqkv, int64_t ldd, float* cspart, int32_t B,
+                                int32_t N, int32_t H, int32_t head_dim, float scale, int32_t dtype, int32_t grid, void* stream);
 #ifdef __cplusplus
 }
 #endif

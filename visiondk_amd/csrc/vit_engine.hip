@@ -14,7 +14,8 @@
 //   GEMM operands / saved tensors   : bf16
 //
 // Classifier mode computes the last block's tail (everything behind its attention) on the class-token rows only, see cls_tail_on().  The switch VDK_VIT_CLS_TAIL
-// decides which rows the forward saves and which the backward reads: it must not change between a forward and its backward.
+// decides which rows the forward saves and which the backward reads: it must not change between a forward and its backward.  The same holds for VDK_VIT_CLS_ATTN
+// (cls_attn_on(): the last block's attention itself on the class query only).
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -53,6 +54,12 @@ int vdk_gemm_fp8_nt_q8(const VdkGemmDesc*, int32_t, int32_t, const float*, const
 int vdk_layernorm_fwd_q8(const float*, int64_t, int32_t, int32_t, const float*, const float*, float, void*, int64_t, float*, float*, void*, int64_t, int32_t, const float*, float*, void*);
 }
 
+
+// attention_cls.hip (C++ linkage): attention of the class query only
+bool vdk_attention_cls_serves(int N, int head_dim);
+int vdk_attention_cls_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, int32_t B, int32_t N, int32_t H, int32_t head_dim, float scale, int opf, int grid, void* stream);
+int vdk_attention_cls_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, void* dqkv, int64_t ldd, float* cspart, int32_t B, int32_t N,
+                          int32_t H, int32_t head_dim, float scale, int opf, int grid, void* stream);
 
 // Operand format of the engine call in progress on this thread: every entry point sets it from VdkVitConfig.operand before it enqueues anything, the helpers below read
 // it (an engine call runs to completion on its thread).  DT16 = the dtype code of the 16-bit tensors.
@@ -280,7 +287,8 @@ static int vit_plan(const VitDims& d, WsPlan* w) {
   w->tA = w_take(cur, trows * tcols * 2); w->tB = w_take(cur, trows * tcols * 2);
   size_t sl = 0;
   {
-    int sh[5][3] = {{(int)M, (int)D, d.T}, {(int)D, (int)M, d.T}, {3 * (int)D, (int)D, d.T}, {(int)D, (int)D, d.T}, {(int)D, d.Kpe, d.B * d.np}};
+    int sh[6][3] = {{(int)M, (int)D, d.T}, {(int)D, (int)M, d.T}, {3 * (int)D, (int)D, d.T}, {(int)D, (int)D, d.T}, {(int)D, d.Kpe, d.B * d.np},
+                    {2 * (int)D, (int)D, d.T} /* the k | v rows of qkv.weight on their own (cls_attn_on) */};
     for (auto& s : sh) {
       int k1 = wgrad_splitk(s[0], s[1], s[2]), k2 = wgrad_splitk_tn(s[0], s[1], s[2]);
       size_t b = (size_t)(k1 > k2 ? k1 : k2) * s[0] * s[1] * 4; if (b > sl) sl = b;
@@ -291,6 +299,7 @@ static int vit_plan(const VitDims& d, WsPlan* w) {
   size_t cs = (size_t)((tcols + 63) / 64) * trows * 4;   // per-row-tile column sums written by the dY transposes ...
   { size_t cs2 = 0; vdk_colsum_bf16_workspace_bytes(d.T, (int)trows, &cs2); if (cs2 > cs) cs = cs2; }   // ... or by vdk_colsum_bf16
   { size_t cs3 = (size_t)2 * ((d.T + 255) / 256) * trows * 4; if (cs3 > cs) cs = cs3; }                  // ... or by a dgrad GEMM's a_colsum / c_colsum by-product
+  { size_t cs4 = (size_t)d.B * 3 * D * 4; if (cs4 > cs) cs = cs4; }                                      // ... or by the attention backward's per-image column sums (small models; cls_attn_on needs them)
   w->csws_bytes = (cs + 255) & ~(size_t)255; w->csws = w_take(cur, 5 * w->csws_bytes);   // slots 0..3: a block's four fused bias-gradient partials (pending until its end), slot 4: immediate users
   w->dhf = w_take(cur, (size_t)d.B * D * 2);
   w->dposall = w_take(cur, (size_t)d.N * D * 4);
@@ -308,6 +317,23 @@ static int vit_plan(const VitDims& d, WsPlan* w) {
 static bool cls_tail_on(const VitDims& d) {
   const char* e = getenv("VDK_VIT_CLS_TAIL");
   return d.C > 0 && d.cls && !d.fp8 && !(e && e[0] == '0');
+}
+
+// the qkv.bias gradient's per-image partials come out of the attention backward (see the call site); VDK_VIT_QKVB_ATTN=0 keeps the separate pass over dqkv
+static bool qkvb_attn_on() {
+  static const bool on = !(getenv("VDK_VIT_QKVB_ATTN") && atoi(getenv("VDK_VIT_QKVB_ATTN")) == 0);
+  return on;
+}
+// Class-query attention: with the tail on, the last block's attention output is read at the class rows only, so its q projection, softmax(q K^T) V, dQ and the q rows
+// of the qkv weight gradient are needed for ONE query per image (csrc/attention_cls.hip); K and V are needed of every token.  Forward: qkv GEMM -> k | v GEMM over all
+// rows (columns D..3D of qkv) + q GEMM on the B class rows; backward: dh1 from the k | v columns of dqkv over all rows, the class rows recomputed with the q columns
+// included; weight gradient likewise in two parts.  The q columns of the other rows of qkv / dqkv, and their o and lse, are never written and never read -- which is
+// why qkv.bias must come from the backward kernel's column-sum by-product (a pass over dqkv would read them): the path needs that by-product's workspace slot.  The
+// forward decides (a query that was not computed cannot be read later), the backward follows it on whatever streams it runs.  VDK_VIT_CLS_ATTN=0 keeps the full-size
+// attention behind the pruned tail; read per call.
+static bool cls_attn_on(const VitDims& d, const WsPlan& w) {
+  const char* e = getenv("VDK_VIT_CLS_ATTN");
+  return cls_tail_on(d) && !(e && e[0] == '0') && qkvb_attn_on() && (size_t)d.B * 3 * d.D * 4 <= w.csws_bytes && vdk_attention_cls_serves(d.N, d.hd);
 }
 
 // ---- fp8 mode (VdkVitConfig.fp8): OCP e4m3 / e5m2 operands for the forward and input-gradient GEMMs of the block Linears ------------------------------------
@@ -504,7 +530,7 @@ int vdk_vit_forward(const VdkVitConfig* cfg, const float* x, const float* params
 
   const float scale = d.scale;  // head_dim ** -0.5
   F8 f8; RC(f8_init(cfg, d, p, &f8, (unsigned char*)(base + w.a8), (unsigned char*)(base + w.a8b)));
-  const bool cls_tail = cls_tail_on(d);
+  const bool cls_tail = cls_tail_on(d), cls_attn = cls_attn_on(d, w);
   for (int l = 0; l < d.L; ++l) {
     const PLayout::Blk& b = p.blk[l];
     float* xin = X + (size_t)(2 * l) * XS; float* xmid = xin + XS; float* xout = xmid + XS;
@@ -529,8 +555,15 @@ int vdk_vit_forward(const VdkVitConfig* cfg, const float* x, const float* params
       continue;
     }
     RC(vdk_layernorm_fwd(xin, D, T, D, params + b.n1w, params + b.n1b, d.eps, h1, D, DT16, mean1, rstd1, s));
-    RC(gemm(s, h1, D, wb + b.qkv_w, D, qkv, 3 * D, T, 3 * D, D, DT16, params + b.qkv_b, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
-    RC(vdk_attention_fwd_dt(qkv, 3 * D, o, D, lse, d.B, d.N, d.H, d.hd, scale, DT16, s));
+    if (cls_attn && l == d.L - 1) {
+      // class-query attention (see cls_attn_on): k | v of every token, q of the class rows (row b * N of h1 / qkv = the same pointer with pitch N * D / N * 3 D)
+      RC(gemm(s, h1, D, wb + b.qkv_w + (size_t)D * D, D, qkv + D, 3 * D, T, 2 * D, D, DT16, params + b.qkv_b + D, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
+      RC(gemm(s, h1, (int64_t)d.N * D, wb + b.qkv_w, D, qkv, (int64_t)d.N * 3 * D, d.B, D, D, DT16, params + b.qkv_b, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
+      if (vdk_attention_cls_fwd(qkv, 3 * D, o, D, lse, d.B, d.N, d.H, d.hd, scale, t_opf, 0, s) != VDK_OK) return vdk_fail(VDK_ELAUNCH, "vdk_vit_forward: class-query attention");
+    } else {
+      RC(gemm(s, h1, D, wb + b.qkv_w, D, qkv, 3 * D, T, 3 * D, D, DT16, params + b.qkv_b, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
+      RC(vdk_attention_fwd_dt(qkv, 3 * D, o, D, lse, d.B, d.N, d.H, d.hd, scale, DT16, s));
+    }
     // class-token tail (last block of a classifier): from here on only row b * N of every image is computed.  The fp32 stream tensors keep those rows where they lie
     // (pitch N * D); h2, g, u hold them packed in their first B rows.  mean2 / rstd2 hold B entries.
     const bool tail = cls_tail && l == d.L - 1;
@@ -654,7 +687,7 @@ int vdk_vit_backward(const VdkVitConfig* cfg, const void* dlogits, const float* 
   const size_t EV_SIDE_DONE = 8;   // slots [8, 8 + L + 2): side stream finished layer l (index l + 1; 0 = embeddings)
   size_t ev_p = EV_SIDE_DONE + d.L + 4;   // producer events, a fresh slot per use
   RC(ev_order(0, s, s2));           // the side stream starts after whatever precedes this call on the main stream
-  const bool cls_tail = cls_tail_on(d);
+  const bool cls_tail = cls_tail_on(d), cls_attn = cls_attn_on(d, w);
 
   // ---- head + final norm -------------------------------------------------------------------------
   bool last_fc2_bias_done = false;   // fc2.bias gradient of block l is produced with DXAB(l): by the final norm's backward (l = L-1) or by block l+1's norm1 backward
@@ -714,12 +747,13 @@ int vdk_vit_backward(const VdkVitConfig* cfg, const void* dlogits, const float* 
     static const bool g16_on = !(getenv("VDK_VIT_G16") && atoi(getenv("VDK_VIT_G16")) == 0);
     const bool g16 = g16_on && ocs_ln && !f8.mode && t_opf == VDK_OPF_F16 && D > 512 && D <= 1024;
     // Class-token tail (see cls_tail_on): down to the proj weight gradient this block works on the B class rows, R rows of pitch ldt; du, h2, g, u hold them packed.
-    // What the full-size kernels below read whole is zero outside those rows: dO (dsm, attention backward) and the dL/dx_mid that the norm1 backward adds (dxmb where the
-    // 16-bit copy is the stream, else the fp32 dxm).  dsm's class rows carry dh2 first, then dO, like the whole tensor does on the full path.
-    const bool tail = cls_tail && l == d.L - 1;
+    // What the full-size kernels below read whole is zero outside those rows: dO (dsm, attention backward; not with the class-query attention, which reads the class
+    // rows of dO only) and the dL/dx_mid that the norm1 backward adds (dxmb where the 16-bit copy is the stream, else the fp32 dxm).  dsm's class rows carry dh2 first,
+    // then dO, like the whole tensor does on the full path.
+    const bool tail = cls_tail && l == d.L - 1, cattn = cls_attn && tail;
     const int R = tail ? d.B : T, Rp = tail ? d.Bp : d.Tp;
     const int64_t ldt = tail ? (int64_t)d.N * D : D;
-    if (tail && (hipMemsetAsync(dsm, 0, XS * 2, s) != hipSuccess || (g16 ? hipMemsetAsync(dxmb, 0, XS * 2, s) : hipMemsetAsync(dxm, 0, XS * 4, s)) != hipSuccess))
+    if (tail && ((!cattn && hipMemsetAsync(dsm, 0, XS * 2, s) != hipSuccess) || (g16 ? hipMemsetAsync(dxmb, 0, XS * 2, s) : hipMemsetAsync(dxm, 0, XS * 4, s)) != hipSuccess))
       return vdk_fail(VDK_ELAUNCH, "vdk_vit_backward: memset failed");
     // MLP branch: dxa / dxab hold dL/dx_out
     RC(ev_order(ev_p++, s, s2));
@@ -787,14 +821,27 @@ int vdk_vit_backward(const VdkVitConfig* cfg, const void* dlogits, const float* 
     // dqkv; with the one-pass small-N kernel the qkv.bias gradient's per-image partials (column sums of the dq | dk | dv rows it stores) come out of the same launch
     // (round 5: the separate pass over dqkv was 13 x 42 us per ViT-B/16 step); VDK_VIT_QKVB_ATTN=0 keeps that pass
     int32_t qkvb_done = 0;
-    {
-      static const bool fuse_on = !(getenv("VDK_VIT_QKVB_ATTN") && atoi(getenv("VDK_VIT_QKVB_ATTN")) == 0);
+    if (cattn) {
+      // class-query attention (see cls_attn_on): dk | dv of every token, dq of the class rows, qkv.bias from the kernel's per-image column sums
+      float* csp = (float*)(base + w.csws + (size_t)3 * w.csws_bytes);
+      if (vdk_attention_cls_bwd(qkv, 3 * D, o, dsm, D, lse, dqkv, 3 * D, csp, d.B, d.N, d.H, d.hd, d.scale, t_opf, 0, s) != VDK_OK)
+        return vdk_fail(VDK_ELAUNCH, "vdk_vit_backward: class-query attention");
+      jobs[nj] = VdkReduceJob{csp, (long)3 * D, d.B, (long)3 * D, grads + b.qkv_b, 1.0f}; ++nj;
+    } else {
+      const bool fuse_on = qkvb_attn_on();
       float* csp = (fuse_on && !f8.mode && one_stream && (size_t)d.B * 3 * D * 4 <= w.csws_bytes) ? (float*)(base + w.csws + (size_t)3 * w.csws_bytes) : nullptr;
       RC(vdk_attention_bwd_cs(qkv, 3 * D, o, dsm, D, lse, dqkv, 3 * D, dvec, d.B, d.N, d.H, d.hd, d.scale, DT16, csp, &qkvb_done, s));
       if (qkvb_done) { jobs[nj] = VdkReduceJob{csp, (long)3 * D, d.B, (long)3 * D, grads + b.qkv_b, 1.0f}; ++nj; }
     }
     RC(ev_order(ev_p++, s, s2));
-    if (f8.mode) {
+    if (cattn) {
+      // dh1 = dqkv . W: the q columns of dqkv are zero outside the class rows, so all rows take the k | v columns (K = 2 D) and the B class rows are then recomputed
+      // over all three (K = 3 D: the same sum the full path forms); the weight gradient likewise: k | v rows of qkv.weight over all tokens, q rows from the class rows
+      RC(gemm(s, dqkv + D, 3 * D, wt + p.blkT[l].qkv + D, 3 * D, dsm, D, T, D, 2 * D, DT16, nullptr, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
+      RC(gemm(s, dqkv, (int64_t)d.N * 3 * D, wt + p.blkT[l].qkv, 3 * D, dsm, (int64_t)d.N * D, d.B, D, 3 * D, DT16, nullptr, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
+      RC(linear_wgrad(s2, d, w, base, dqkv + D, 3 * D, h1, D, T, d.Tp, 2 * D, D, grads + b.qkv_w + (size_t)D * D, nullptr, 0));
+      RC(linear_wgrad(s2, d, w, base, dqkv, (int64_t)d.N * 3 * D, h1, (int64_t)d.N * D, d.B, d.Bp, D, D, grads + b.qkv_w, nullptr, 0));
+    } else if (f8.mode) {
       // dqkv is attention's output: its column sums (qkv.bias) and its e5m2 copy (operand of the dh1 GEMM) come from ONE pass over it
       size_t csneed = 0; vdk_colsum_bf16_workspace_bytes(T, 3 * D, &csneed);
       const bool fcq = f8_fused(f8) && one_stream && csneed <= w.csws_bytes;
