@@ -272,6 +272,10 @@ INTERNAL = {
     "vdk_debug_reduce_rows_job": (C.c_int, [P, I64, I32, I64, P, F32, P]),
     "vdk_debug_attention_cls_fwd": (C.c_int, [P, I64, P, I64, P, I32, I32, I32, I32, F32, I32, I32, P]),
     "vdk_debug_attention_cls_bwd": (C.c_int, [P, I64, P, P, I64, P, P, I64, P, I32, I32, I32, I32, F32, I32, I32, P]),
+    "vdk_debug_attention_hd_fwd": (C.c_int, [P, I64, P, I64, P, I32, I32, I32, I32, F32, I32, P]),
+    "vdk_debug_attention_hd_bwd": (C.c_int, [P, I64, P, P, I64, P, P, I64, P, I32, I32, I32, I32, F32, I32, P]),
+    "vdk_attn_pool_fwd_hd": (C.c_int, [P, P, I64, I32, I32, I32, I32, F32, P, I64, P, I32, P]),
+    "vdk_attn_pool_bwd_hd": (C.c_int, [P, P, I64, P, P, I64, I32, I32, I32, I32, F32, P, I64, P, I32, P]),
 }
 
 

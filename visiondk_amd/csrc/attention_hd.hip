@@ -1,5 +1,5 @@
 // attention_hd.hip — K3 forward and backward for head dimensions beyond 64, with the head dimension HD as a template parameter.  Instantiated and dispatched for
-// HD = 80 only (ViT-H/14 CLIP: 1280 / 16 heads).  Same operator and operand contract as attention.hip / attention_small.hip / attention_long.hip:
+// HD = 80 (ViT-H/14 CLIP: 1280 / 16 heads) and HD = 72 (SigLIP SO400M/14: 1152 / 16 heads; the ragged instance, see below).  Same operator and operand contract as attention.hip / attention_small.hip / attention_long.hip:
 // softmax(q k^T / sqrt(hd)) v on 16-bit [B, N, 3, H, hd] rows of arbitrary (% 8) pitch, lse and D in fp32, and the same rounding points (scores and statistics in fp32,
 // exp2 with scale * log2(e) folded in, P / O / dS rounded once, the backward consumes the forward's own 16-bit o and lse).
 //
@@ -27,19 +27,25 @@
 // products whose OUTPUT is HD wide (P V, dS K, dO^T P, Q^T dS); q k^T and dO v^T contract over HD in exactly 5 steps.
 //
 // LDS per workgroup: 2 x 24 KB chunk buffers (+ 2 x 1 KB lse / D in the kv kernel) + 4 wave store tiles of 32 x 176 bytes = 70.5 / 72.5 KB: two workgroups per CU.
-// A narrower head (72) can follow as an instance that zero-fills columns HD .. 79 of an 80-wide tile; nothing but 80 is instantiated here.
+//
+// HD = 72 is the 80-wide geometry with a ragged last contraction step: 9 chunks per row in the same 12 slots (pad slots 9 .. 11 hold copies of chunks 5 .. 7), KS = 5, and
+// step 4 covers columns 64 .. 79 of which 72 .. 79 do not exist.  Every contraction over the head dimension (q k^T, dO v^T, K q^T, V dO^T, and the D = rowsum(dO * O) sum)
+// has exactly one own-row operand that comes from global: its upper half-wave does not issue the load of columns 72 .. 79 (they are the next head's, or lie outside the
+// operand) and holds an exact zero there (ah_own_frag), so whatever the streamed side's slot 9 holds -- a copy of the row's own finite chunk 5 -- contributes exactly 0.
+// The products whose output is HD wide still produce columns 72 .. 95 from copies; ah_store_tile drops everything from column HD on.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include "vdk_device.h"
 #include "vdk_host.h"
+#include "vdk_internal.h"
 
 #define AH_CT 2                            // 32-row tiles per chunk
 #define AH_CROWS (32 * AH_CT)              // 64 rows: a multiple of 16, so the swizzle of a chunk-local row equals the one of the global row
 
 template <int HD>
 struct AhGeom {
-  static_assert(HD % 16 == 0 && HD > 64 && HD <= 96, "attention_hd: head dimensions 80 and 96 fit this layout");
-  static constexpr int KS = HD / 16;                  // contraction steps of a 32x32x16 MFMA over the head dimension
+  static_assert(HD % 8 == 0 && HD > 64 && HD <= 96, "attention_hd: head dimensions 72 .. 96 fit this layout");
+  static constexpr int KS = (HD + 15) / 16;           // contraction steps of a 32x32x16 MFMA over the head dimension (HD % 16 == 8: the last one is half empty)
   static constexpr int CH = HD / 8;                   // 16-byte chunks of a row
   static constexpr int PCH = (CH + 3) & ~3;           // chunk slots of a staged row
   static constexpr int ROW = PCH * 16;                // bytes per staged row
@@ -90,6 +96,14 @@ __device__ __forceinline__ AhLane<HD> ah_lane(int lane) {
     a.tr[dh][1] = r2 * G::ROW + (ah_pos(r2, byte >> 4) << 4) + (byte & 8);
   }
   return a;
+}
+// own-row fragment from global: the 16 bytes at k = 16 ks + 8 hi of the row at `row`.  HD % 16 == 8: the upper half-wave of the last step takes an exact zero and issues
+// no load (those bytes are not the head's)
+template <int HD>
+__device__ __forceinline__ s16x8 ah_own_frag(const bf16_t* __restrict__ row, int ks, int hi) {
+  if (HD % 16 == 0 || ks < AhGeom<HD>::KS - 1 || hi == 0) return *(const s16x8*)(row + ks * 16 + hi * 8);
+  const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+  return z;
 }
 // MFMA A/B fragment of the 32-row tile at `tile`: lane (row, hi) -> the 16 bytes at k = 16 ks + 8 hi
 template <int HD>
@@ -177,7 +191,7 @@ __global__ __launch_bounds__(256, 2) void attn_h_fwd_kernel(const bf16_t* __rest
     const int qr = qrow < N ? qrow : N - 1;
     s16x8 qf[GE::KS];
 #pragma unroll
-    for (int ks = 0; ks < GE::KS; ++ks) qf[ks] = *(const s16x8*)(q + off + (long)qr * ld + ks * 16 + hi * 8);
+    for (int ks = 0; ks < GE::KS; ++ks) qf[ks] = ah_own_frag<HD>(q + off + (long)qr * ld, ks, hi);
     const int tn = t + tstride;
     const int itemn = (tn / G) * 8 + x;
     const long offn = (long)(itemn / H) * N * ld + (itemn % H) * HD;
@@ -291,9 +305,10 @@ __global__ __launch_bounds__(256, 2) void attn_h_bwd_q_kernel(const bf16_t* __re
     float dsum = 0.f;
 #pragma unroll
     for (int ks = 0; ks < GE::KS; ++ks) {
-      qf[ks] = *(const s16x8*)(q + off + (long)qr * ld + ks * 16 + hi * 8);
-      gf[ks] = *(const s16x8*)(dout + offo + (long)qr * ldo + ks * 16 + hi * 8);
-      const u32x4 of = *(const u32x4*)(o + offo + (long)qr * ldo + ks * 16 + hi * 8);
+      qf[ks] = ah_own_frag<HD>(q + off + (long)qr * ld, ks, hi);
+      gf[ks] = ah_own_frag<HD>(dout + offo + (long)qr * ldo, ks, hi);
+      const s16x8 os = ah_own_frag<HD>(o + offo + (long)qr * ldo, ks, hi);
+      const u32x4 of = *(const u32x4*)&os;
       const u32x4 gu = *(const u32x4*)&gf[ks];
 #pragma unroll
       for (int e = 0; e < 4; ++e) { dsum = fmaf(op_lo<OF>(gu[e]), op_lo<OF>(of[e]), dsum); dsum = fmaf(op_hi<OF>(gu[e]), op_hi<OF>(of[e]), dsum); }
@@ -388,7 +403,7 @@ __global__ __launch_bounds__(256, 2) void attn_h_bwd_kv_kernel(const bf16_t* __r
     const long kr = (long)(krow < N ? krow : N - 1) * ld;
     s16x8 kf[GE::KS], vf[GE::KS];
 #pragma unroll
-    for (int ks = 0; ks < GE::KS; ++ks) { kf[ks] = *(const s16x8*)(k + off + kr + ks * 16 + hi * 8); vf[ks] = *(const s16x8*)(v + off + kr + ks * 16 + hi * 8); }
+    for (int ks = 0; ks < GE::KS; ++ks) { kf[ks] = ah_own_frag<HD>(k + off + kr, ks, hi); vf[ks] = ah_own_frag<HD>(v + off + kr, ks, hi); }
     const int tn = t + tstride;
     const int itemn = (tn / G) * 8 + x;
     const long offn = (long)(itemn / H) * N * ld + (itemn % H) * HD, offon = (long)(itemn / H) * N * ldo + (itemn % H) * HD;
@@ -504,14 +519,46 @@ static int ah_launch_bwd(const void* qkv, int64_t ld, const void* o, const void*
   return VDK_OK;
 }
 
-// in-library entry points (attention.hip routes head_dim == 80 here); any other head_dim: VDK_EUNSUPPORTED
+// in-library entry points (attention.hip routes head_dim == 80 here, the ViT engine head_dim == 72 as well); any other head_dim: VDK_EUNSUPPORTED
 int vdk_attention_hd_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, int32_t B, int32_t N, int32_t H, int32_t head_dim, float scale, int opf, void* stream) {
-  if (head_dim != 80) return VDK_EUNSUPPORTED;
-  return opf ? ah_launch_fwd<VDK_OPF_F16, 80>(qkv, ld, o, ldo, lse, B, N, H, scale, stream) : ah_launch_fwd<VDK_OPF_BF16, 80>(qkv, ld, o, ldo, lse, B, N, H, scale, stream);
+  if (head_dim == 80)
+    return opf ? ah_launch_fwd<VDK_OPF_F16, 80>(qkv, ld, o, ldo, lse, B, N, H, scale, stream) : ah_launch_fwd<VDK_OPF_BF16, 80>(qkv, ld, o, ldo, lse, B, N, H, scale, stream);
+  if (head_dim == 72)
+    return opf ? ah_launch_fwd<VDK_OPF_F16, 72>(qkv, ld, o, ldo, lse, B, N, H, scale, stream) : ah_launch_fwd<VDK_OPF_BF16, 72>(qkv, ld, o, ldo, lse, B, N, H, scale, stream);
+  return VDK_EUNSUPPORTED;
 }
 int vdk_attention_hd_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, void* dqkv, int64_t ldd, float* dvec, int32_t B, int32_t N,
                          int32_t H, int32_t head_dim, float scale, int opf, void* stream) {
-  if (head_dim != 80) return VDK_EUNSUPPORTED;
-  return opf ? ah_launch_bwd<VDK_OPF_F16, 80>(qkv, ld, o, dout, ldo, lse, dqkv, ldd, dvec, B, N, H, scale, stream)
-             : ah_launch_bwd<VDK_OPF_BF16, 80>(qkv, ld, o, dout, ldo, lse, dqkv, ldd, dvec, B, N, H, scale, stream);
+  if (head_dim == 80)
+    return opf ? ah_launch_bwd<VDK_OPF_F16, 80>(qkv, ld, o, dout, ldo, lse, dqkv, ldd, dvec, B, N, H, scale, stream)
+               : ah_launch_bwd<VDK_OPF_BF16, 80>(qkv, ld, o, dout, ldo, lse, dqkv, ldd, dvec, B, N, H, scale, stream);
+  if (head_dim == 72)
+    return opf ? ah_launch_bwd<VDK_OPF_F16, 72>(qkv, ld, o, dout, ldo, lse, dqkv, ldd, dvec, B, N, H, scale, stream)
+               : ah_launch_bwd<VDK_OPF_BF16, 72>(qkv, ld, o, dout, ldo, lse, dqkv, ldd, dvec, B, N, H, scale, stream);
+  return VDK_EUNSUPPORTED;
 }
+
+extern "C" {
+
+// vdk_internal.h: the kernels of this file behind the argument lists of vdk_attention_fwd_dt / vdk_attention_bwd_dt, for the kernel-level tests and tools/bench_attention.py
+// (the public entries keep refusing head_dim 72; the ViT engine reaches it in-library)
+int vdk_debug_attention_hd_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, int32_t B, int32_t N, int32_t H, int32_t head_dim, float scale, int32_t dtype,
+                               void* stream) {
+  if (!qkv || !o || B <= 0 || N <= 0 || H <= 0 || (dtype != VDK_BF16 && dtype != VDK_F16)) return vdk_fail(VDK_EINVAL, "vdk_debug_attention_hd_fwd: bad argument");
+  if (head_dim != 72 && head_dim != 80) return vdk_fail(VDK_EUNSUPPORTED, "vdk_debug_attention_hd_fwd: head_dim must be 72 or 80");
+  if ((ld & 7) || (ldo & 7) || ld < 3L * H * head_dim || ldo < (long)H * head_dim) return vdk_fail(VDK_EINVAL, "vdk_debug_attention_hd_fwd: ld % 8, ld >= 3 * H * head_dim");
+  const int rc = vdk_attention_hd_fwd(qkv, ld, o, ldo, lse, B, N, H, head_dim, scale, dtype == VDK_F16 ? VDK_OPF_F16 : VDK_OPF_BF16, stream);
+  return rc ? rc : vdk_check_launch("vdk_debug_attention_hd_fwd");
+}
+int vdk_debug_attention_hd_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, void* dqkv, int64_t lddqkv, float* dvec, int32_t B,
+                               int32_t N, int32_t H, int32_t head_dim, float scale, int32_t dtype, void* stream) {
+  if (!qkv || !o || !dout || !lse || !dqkv || !dvec || B <= 0 || N <= 0 || H <= 0 || (dtype != VDK_BF16 && dtype != VDK_F16))
+    return vdk_fail(VDK_EINVAL, "vdk_debug_attention_hd_bwd: bad argument");
+  if (head_dim != 72 && head_dim != 80) return vdk_fail(VDK_EUNSUPPORTED, "vdk_debug_attention_hd_bwd: head_dim must be 72 or 80");
+  if ((ld & 7) || (ldo & 7) || (lddqkv & 7) || ld < 3L * H * head_dim || lddqkv < 3L * H * head_dim || ldo < (long)H * head_dim)
+    return vdk_fail(VDK_EINVAL, "vdk_debug_attention_hd_bwd: ld % 8, ld >= 3 * H * head_dim");
+  const int rc = vdk_attention_hd_bwd(qkv, ld, o, dout, ldo, lse, dqkv, lddqkv, dvec, B, N, H, head_dim, scale, dtype == VDK_F16 ? VDK_OPF_F16 : VDK_OPF_BF16, stream);
+  return rc ? rc : vdk_check_launch("vdk_debug_attention_hd_bwd");
+}
+
+}  // extern "C"

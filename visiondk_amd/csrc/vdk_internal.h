@@ -31,6 +31,18 @@ int vdk_debug_attention_cls_fwd(const void* qkv, int64_t ld, void* o, int64_t ld
                                 int32_t grid, void* stream);
 int vdk_debug_attention_cls_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, void* dqkv, int64_t ldd, float* cspart, int32_t B,
                                 int32_t N, int32_t H, int32_t head_dim, float scale, int32_t dtype, int32_t grid, void* stream);
+/* tests / tools: the streaming attention kernels of csrc/attention_hd.hip behind the argument lists of vdk_attention_fwd_dt / vdk_attention_bwd_dt.  head_dim 72 or 80, anything
+ * else VDK_EUNSUPPORTED.  The public entries keep refusing 72; the ViT engine reaches the 72-wide instance in-library. */
+int vdk_debug_attention_hd_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, int32_t B, int32_t N, int32_t H, int32_t head_dim, float scale, int32_t dtype,
+                               void* stream);
+int vdk_debug_attention_hd_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, void* dqkv, int64_t lddqkv, float* dvec, int32_t B,
+                               int32_t N, int32_t H, int32_t head_dim, float scale, int32_t dtype, void* stream);
+/* vdk_attn_pool_fwd_dt / vdk_attn_pool_bwd_dt with the head dimension as an argument: 64 (the same kernels and bits as the public entries), 72 (SigLIP SO400M) or 80; anything
+ * else VDK_EUNSUPPORTED.  q f32 [H*head_dim]; kv / dkv 16-bit [B*N, 2*H*head_dim], ldkv and lddkv >= 2*H*head_dim; out / dout / dq_part f32 [B, H*head_dim]. */
+int vdk_attn_pool_fwd_hd(const float* q, const void* kv, int64_t ldkv, int32_t B, int32_t N, int32_t H, int32_t head_dim, float scale, float* out, int64_t ldo, float* probs,
+                         int32_t dtype, void* stream);
+int vdk_attn_pool_bwd_hd(const float* q, const void* kv, int64_t ldkv, const float* probs, const float* dout, int64_t lddo, int32_t B, int32_t N, int32_t H, int32_t head_dim,
+                         float scale, void* dkv, int64_t lddkv, float* dq_part, int32_t dtype, void* stream);
 #ifdef __cplusplus
 }
 #endif

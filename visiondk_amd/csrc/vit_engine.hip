@@ -61,6 +61,12 @@ int vdk_attention_cls_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, flo
 int vdk_attention_cls_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, void* dqkv, int64_t ldd, float* cspart, int32_t B, int32_t N,
                           int32_t H, int32_t head_dim, float scale, int opf, int grid, void* stream);
 
+// attention_hd.hip (C++ linkage): the streaming kernels for head dims 72 and 80.  The public vdk_attention_* entries route 80 there themselves and refuse 72 (their
+// contract is "64 or 80"); the engine reaches the 72-wide instance here, as it reaches attention_cls.hip.
+int vdk_attention_hd_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, int32_t B, int32_t N, int32_t H, int32_t head_dim, float scale, int opf, void* stream);
+int vdk_attention_hd_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, void* dqkv, int64_t ldd, float* dvec, int32_t B, int32_t N,
+                         int32_t H, int32_t head_dim, float scale, int opf, void* stream);
+
 // Operand format of the engine call in progress on this thread: every entry point sets it from VdkVitConfig.operand before it enqueues anything, the helpers below read
 // it (an engine call runs to completion on its thread).  DT16 = the dtype code of the 16-bit tensors.
 static thread_local int t_opf = VDK_OPF_BF16;
@@ -80,7 +86,7 @@ static bool gelu_saved_grad() {
 static inline int64_t up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
 struct VitDims {
-  int B, img, ps, Cin, D, L, H, M, C, Cp, np, N, T, Kraw, Kpe, Tp, Bp, cls, pre /* VdkVitConfig.pre_norm */, hd /* head dim: 64 or 80 */, fp8, opf /* operand format: VDK_OPF_BF16 | VDK_OPF_F16 (VdkVitConfig.operand) */;   // cls: 1 = class token in row 0 of every image's token block   // Kraw = in_chans * patch^2, Kpe = Kraw padded to 8 (patch 14: 588 -> 592)
+  int B, img, ps, Cin, D, L, H, M, C, Cp, np, N, T, Kraw, Kpe, Tp, Bp, cls, pre /* VdkVitConfig.pre_norm */, hd /* head dim: 64, 72 or 80 */, fp8, opf /* operand format: VDK_OPF_BF16 | VDK_OPF_F16 (VdkVitConfig.operand) */;   // cls: 1 = class token in row 0 of every image's token block   // Kraw = in_chans * patch^2, Kpe = Kraw padded to 8 (patch 14: 588 -> 592)
   float eps, scale /* hd ** -0.5 */;
 };
 static int vit_dims(const VdkVitConfig* c, VitDims* d) {
@@ -89,7 +95,8 @@ static int vit_dims(const VdkVitConfig* c, VitDims* d) {
   d->H = c->heads; d->M = c->mlp_dim; d->C = c->num_classes; d->eps = c->ln_eps;
   if (d->B <= 0 || d->img <= 0 || d->ps <= 0 || d->img % d->ps || d->Cin <= 0 || d->D <= 0 || d->L <= 0 || d->H <= 0 || d->M <= 0 || d->C < 0)
     return vdk_fail(VDK_EINVAL, "vit: bad config value");
-  if (d->D != d->H * 64 && d->D != d->H * 80) return vdk_fail(VDK_EUNSUPPORTED, "vit: head_dim must be 64 or 80 (dim == 64 * heads or 80 * heads)");
+  if (d->D != d->H * 64 && d->D != d->H * 72 && d->D != d->H * 80)
+    return vdk_fail(VDK_EUNSUPPORTED, "vit: head_dim must be 64, 72 or 80 (dim == 64 * heads, 72 * heads or 80 * heads)");
   d->hd = d->D / d->H;
   d->scale = 1.0f / sqrtf((float)d->hd);
   if ((d->D & 7) || (d->M & 7)) return vdk_fail(VDK_EUNSUPPORTED, "vit: dim and mlp_dim must be multiples of 8");
@@ -109,9 +116,25 @@ static int vit_dims(const VdkVitConfig* c, VitDims* d) {
   if (d->fp8 < 0 || d->fp8 > 2) return vdk_fail(VDK_EINVAL, "vit: fp8 must be 0, 1 or 2");
   if (c->operand != VDK_BF16 && c->operand != VDK_F16) return vdk_fail(VDK_EINVAL, "vit: operand must be VDK_BF16 or VDK_F16");
   d->opf = c->operand == VDK_F16 ? VDK_OPF_F16 : VDK_OPF_BF16;
+  if (d->fp8 && d->hd == 72) return vdk_fail(VDK_EUNSUPPORTED, "vit: the fp8 mode does not serve head_dim 72");
   if (d->opf && d->fp8) return vdk_fail(VDK_EUNSUPPORTED, "vit: the fp8 mode goes with bf16 operands");
   if (d->fp8 && (d->D < 256 || (d->D % 128) || (d->M % 128))) return vdk_fail(VDK_EUNSUPPORTED, "vit: the fp8 mode needs dim >= 256, dim and mlp_dim % 128 == 0");
   return VDK_OK;
+}
+
+// full attention of one block: head dim 72 in-library, 64 and 80 through the public entries.  The backward hands back the qkv.bias partials where the chosen kernel
+// produces them (*produced; never at 72 and 80: the caller then sums dqkv itself)
+static int attn_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, const VitDims& d, int32_t dtype, void* stream) {
+  if (d.hd != 72) return vdk_attention_fwd_dt(qkv, ld, o, ldo, lse, d.B, d.N, d.H, d.hd, d.scale, dtype, stream);
+  const int rc = vdk_attention_hd_fwd(qkv, ld, o, ldo, lse, d.B, d.N, d.H, d.hd, d.scale, dtype == VDK_F16 ? VDK_OPF_F16 : VDK_OPF_BF16, stream);
+  return rc ? vdk_fail(rc, "vit: attention forward at head_dim 72") : vdk_check_launch("vit: attention forward at head_dim 72");
+}
+static int attn_bwd_cs(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, void* dqkv, int64_t ldd, float* dvec, const VitDims& d,
+                       int32_t dtype, float* cspart, int32_t* produced, void* stream) {
+  if (d.hd != 72) return vdk_attention_bwd_cs(qkv, ld, o, dout, ldo, lse, dqkv, ldd, dvec, d.B, d.N, d.H, d.hd, d.scale, dtype, cspart, produced, stream);
+  *produced = 0;
+  const int rc = vdk_attention_hd_bwd(qkv, ld, o, dout, ldo, lse, dqkv, ldd, dvec, d.B, d.N, d.H, d.hd, d.scale, dtype == VDK_F16 ? VDK_OPF_F16 : VDK_OPF_BF16, stream);
+  return rc ? vdk_fail(rc, "vit: attention backward at head_dim 72") : vdk_check_launch("vit: attention backward at head_dim 72");
 }
 
 // ---------------------------------------------------------------------------- parameter layout
@@ -562,7 +585,7 @@ int vdk_vit_forward(const VdkVitConfig* cfg, const float* x, const float* params
       if (vdk_attention_cls_fwd(qkv, 3 * D, o, D, lse, d.B, d.N, d.H, d.hd, scale, t_opf, 0, s) != VDK_OK) return vdk_fail(VDK_ELAUNCH, "vdk_vit_forward: class-query attention");
     } else {
       RC(gemm(s, h1, D, wb + b.qkv_w, D, qkv, 3 * D, T, 3 * D, D, DT16, params + b.qkv_b, nullptr, 0, VDK_ACT_NONE, nullptr, 0, 1, 0, nullptr, 0));
-      RC(vdk_attention_fwd_dt(qkv, 3 * D, o, D, lse, d.B, d.N, d.H, d.hd, scale, DT16, s));
+      RC(attn_fwd(qkv, 3 * D, o, D, lse, d, DT16, s));
     }
     // class-token tail (last block of a classifier): from here on only row b * N of every image is computed.  The fp32 stream tensors keep those rows where they lie
     // (pitch N * D); h2, g, u hold them packed in their first B rows.  mean2 / rstd2 hold B entries.
@@ -830,7 +853,7 @@ int vdk_vit_backward(const VdkVitConfig* cfg, const void* dlogits, const float* 
     } else {
       const bool fuse_on = qkvb_attn_on();
       float* csp = (fuse_on && !f8.mode && one_stream && (size_t)d.B * 3 * D * 4 <= w.csws_bytes) ? (float*)(base + w.csws + (size_t)3 * w.csws_bytes) : nullptr;
-      RC(vdk_attention_bwd_cs(qkv, 3 * D, o, dsm, D, lse, dqkv, 3 * D, dvec, d.B, d.N, d.H, d.hd, d.scale, DT16, csp, &qkvb_done, s));
+      RC(attn_bwd_cs(qkv, 3 * D, o, dsm, D, lse, dqkv, 3 * D, dvec, d, DT16, csp, &qkvb_done, s));
       if (qkvb_done) { jobs[nj] = VdkReduceJob{csp, (long)3 * D, d.B, (long)3 * D, grads + b.qkv_b, 1.0f}; ++nj; }
     }
     RC(ev_order(ev_p++, s, s2));
@@ -962,8 +985,8 @@ int vdk_vit_workspace_f32_bytes(const VdkVitConfig* cfg, size_t* bytes) {
 int vdk_vit_forward_f32(const VdkVitConfig* cfg, const float* x, const float* params, void* ws, size_t ws_bytes, float* logits, void* stream_) {
   hipStream_t s = (hipStream_t)stream_;
   VitDims d; RC(vit_dims(cfg, &d));
-  // The stem GEMM reads the patch rows and the [D, Kraw] master weight as they lie: vdk_gemm_f32_nt needs K % 4 only (patch 14: 588).  The head-dim-80 models
-  // (ViT-H/14) are served on that rule; at head dim 64 the older K % 8 refusal stands unchanged (tests/test_vit.py pins it for the patch-14 ids there).
+  // The stem GEMM reads the patch rows and the [D, Kraw] master weight as they lie: vdk_gemm_f32_nt needs K % 4 only (patch 14: 588).  The head-dim-72 and -80 models
+  // (SigLIP SO400M/14, ViT-H/14) are served on that rule; at head dim 64 the older K % 8 refusal stands unchanged (tests/test_vit.py pins it for the patch-14 ids there).
   if (d.Kraw & 3) return vdk_fail(VDK_EUNSUPPORTED, "vdk_vit_forward_f32: in_chans*patch*patch must be a multiple of 4 on the fp32 path");
   if (d.hd == 64 && d.Kraw != d.Kpe) return vdk_fail(VDK_EUNSUPPORTED, "vdk_vit_forward_f32: in_chans*patch*patch must be a multiple of 8 on the fp32 path");
   PLayout p; RC(vit_layout(d, &p));

@@ -39,7 +39,7 @@ class VitSpec:
     pre_norm: bool = False        # timm pre_norm=True (the CLIP ViTs): LayerNorm `norm_pre` in front of the blocks, patch embedding without a bias
 
 
-# timm 0.9.16 model ids the engine covers (head_dim 64, or 80 for ViT-H/14: csrc/attention_hd.hip; patch 14 works through zero-padded operand copies of the patch-embedding weight)
+# timm 0.9.16 model ids the engine covers (head_dim 64, or 80 for ViT-H/14 and 72 for SigLIP SO400M/14: csrc/attention_hd.hip; patch 14 works through zero-padded operand copies of the patch-embedding weight)
 TIMM_VITS = {
     "vit_tiny_patch16_224": dict(dim=192, depth=12, heads=3, mlp_dim=768),
     "vit_small_patch16_224": dict(dim=384, depth=12, heads=6, mlp_dim=1536),
@@ -62,6 +62,9 @@ TIMM_VITS = {
     "vit_base_patch16_siglip_224": dict(dim=768, depth=12, heads=12, mlp_dim=3072, class_token=False),
     "vit_large_patch16_siglip_256": dict(dim=1024, depth=24, heads=16, mlp_dim=4096, img_size=256, class_token=False),
     "vit_large_patch14_siglip_336": dict(dim=1024, depth=24, heads=16, mlp_dim=4096, patch_size=14, img_size=336, class_token=False),   # BASELINE.json configs[4]'s geometry
+    # SigLIP SO400M/14 (`timm-vit_so400m_patch14_siglip_224.webli` in the shipped YAMLs): head_dim 1152 / 16 = 72, mlp int(1152 * 3.7362) = 4304, 256 tokens.  (The 384 px id is
+    # not here: 384 is no multiple of 14 and the stem does not handle the cropped border.)
+    "vit_so400m_patch14_siglip_224": dict(dim=1152, depth=27, heads=16, mlp_dim=4304, patch_size=14, class_token=False),
 }
 
 
@@ -435,7 +438,11 @@ class _AttnPoolFn(torch.autograd.Function):
         q = ops.gemm_f32(latent.detach().reshape(1, D).contiguous(), q_w.detach(), bias=q_b.detach(), backend=be).view(D)
         pooled = torch.empty((B, D), dtype=torch.float32, device=dev)
         probs = torch.empty((B, H, N), dtype=torch.float32, device=dev)
-        be.check(be.lib.vdk_attn_pool_fwd_dt(be.ptr(q), be.ptr(kv), 2 * D, B, N, H, mod.scale, be.ptr(pooled), D, be.ptr(probs), ops._dt(odt), be.stream()), "vdk_attn_pool_fwd")
+        if mod.head_dim == 64:
+            be.check(be.lib.vdk_attn_pool_fwd_dt(be.ptr(q), be.ptr(kv), 2 * D, B, N, H, mod.scale, be.ptr(pooled), D, be.ptr(probs), ops._dt(odt), be.stream()), "vdk_attn_pool_fwd")
+        else:
+            be.check(be.lib.vdk_attn_pool_fwd_hd(be.ptr(q), be.ptr(kv), 2 * D, B, N, H, mod.head_dim, mod.scale, be.ptr(pooled), D, be.ptr(probs), ops._dt(odt), be.stream()),
+                     "vdk_attn_pool_fwd_hd")
         y1 = ops.gemm_f32(pooled, proj_w.detach(), bias=proj_b.detach(), backend=be)
         h, mean, rstd = ops.layernorm_fwd(y1, n_w.detach(), n_b.detach(), eps=mod.eps, out_dtype=torch.float32, backend=be)
         u = ops.gemm_f32(h, fc1_w.detach(), bias=fc1_b.detach(), backend=be)
@@ -465,8 +472,12 @@ class _AttnPoolFn(torch.autograd.Function):
         odt = kv.dtype
         dkv = torch.empty((B * N, 2 * D), dtype=odt, device=dev)
         dq_part = torch.empty((B, D), dtype=torch.float32, device=dev)
-        be.check(be.lib.vdk_attn_pool_bwd_dt(be.ptr(q), be.ptr(kv), 2 * D, be.ptr(probs), be.ptr(dpooled), D, B, N, H, mod.scale, be.ptr(dkv), 2 * D, be.ptr(dq_part),
-                                             ops._dt(odt), be.stream()), "vdk_attn_pool_bwd")
+        if mod.head_dim == 64:
+            be.check(be.lib.vdk_attn_pool_bwd_dt(be.ptr(q), be.ptr(kv), 2 * D, be.ptr(probs), be.ptr(dpooled), D, B, N, H, mod.scale, be.ptr(dkv), 2 * D, be.ptr(dq_part),
+                                                 ops._dt(odt), be.stream()), "vdk_attn_pool_bwd")
+        else:
+            be.check(be.lib.vdk_attn_pool_bwd_hd(be.ptr(q), be.ptr(kv), 2 * D, be.ptr(probs), be.ptr(dpooled), D, B, N, H, mod.head_dim, mod.scale, be.ptr(dkv), 2 * D,
+                                                 be.ptr(dq_part), ops._dt(odt), be.stream()), "vdk_attn_pool_bwd_hd")
         dq = ops.reduce_rows(dq_part, backend=be)                          # [D]
         lat = latent.detach().reshape(1, D)
         dq_w, dq_b = dq.view(D, 1) * lat, dq
@@ -489,16 +500,18 @@ class _AttnPoolFn(torch.autograd.Function):
 
 class AttentionPoolLatent(nn.Module):
     """timm.layers.AttentionPoolLatent as the SigLIP ViTs configure it (latent_len 1, qkv_bias, no qk_norm, LayerNorm eps 1e-6, mlp_ratio 4, exact GELU, pool 'token');
-    parameter names equal timm's (latent, q, kv, proj, norm, mlp.fc1, mlp.fc2).  head_dim 64."""
+    parameter names equal timm's (latent, q, kv, proj, norm, mlp.fc1, mlp.fc2).  head_dim 64 (the public vdk_attn_pool_*_dt entries), 72 or 80 (the _hd entries of
+    csrc/vdk_internal.h)."""
 
     def __init__(self, dim: int, num_heads: int, mlp_dim: Optional[int] = None, eps: float = 1e-6, backend: Optional[_lib.Backend] = None, device=None,
                  generator: Optional[torch.Generator] = None, op_dtype=torch.bfloat16):
         super().__init__()
-        assert dim == num_heads * 64, "head_dim must be 64"
+        assert dim % num_heads == 0 and dim // num_heads in (64, 72, 80), "head_dim must be 64, 72 or 80"
         self.op_dtype = op_dtype             # 16-bit format of the kv Linear's operands and of kv / dkv (the trunk's)
         self.be = backend or _lib.load()
         dev = device if device is not None else ("cuda" if self.be.device_only else "cpu")
-        self.num_heads, self.scale, self.eps = num_heads, 0.125, eps
+        self.num_heads, self.head_dim, self.eps = num_heads, dim // num_heads, eps
+        self.scale = self.head_dim ** -0.5
         mlp_dim = mlp_dim or 4 * dim
         self.latent = nn.Parameter(torch.empty(1, 1, dim, device=dev))
         self.q, self.kv, self.proj = _Holder(), _Holder(), _Holder()
