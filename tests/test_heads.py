@@ -1,7 +1,11 @@
 """K11 margin heads vs the golden outputs of the REFERENCE's own ArcFace / CircleLoss / MV_Softmax modules
 (tests/golden/heads.npz, made by tests/golden/make_golden.py).  The GEMMs use bf16 MFMA operands: cos errors of a few 1e-4
 are amplified by the scale (32 / 256) in the logits, so logits are compared in units of the scale; gradients flow through
-single-plane bf16 GEMMs (dcos, f^, W^ rounded to bf16): 2e-3 ... 3e-3 relative against the reference's modules (bound 8e-3)."""
+single-plane bf16 GEMMs (dcos, f^, W^ rounded to bf16): 2e-3 ... 3e-3 relative against the reference's modules (bound 8e-3).
+
+These are whole-tensor norms on Gaussian features, and most cases compare one form of the head with another: one wrong class column or an error of the shared margin
+functions stays below them.  Every dcos entry, dW column and dfeats row is bounded against a float64 restatement of the reference's modules in
+tests/test_head_entries.py (the ABI entries on planted cosines) and tests/test_head_columns.py (end to end on planted heads); helpers in tests/headbound.py."""
 from pathlib import Path
 
 import numpy as np
