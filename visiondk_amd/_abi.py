@@ -276,6 +276,10 @@ INTERNAL = {
     "vdk_debug_attention_hd_bwd": (C.c_int, [P, I64, P, P, I64, P, P, I64, P, I32, I32, I32, I32, F32, I32, P]),
     "vdk_attn_pool_fwd_hd": (C.c_int, [P, P, I64, I32, I32, I32, I32, F32, P, I64, P, I32, P]),
     "vdk_attn_pool_bwd_hd": (C.c_int, [P, P, I64, P, P, I64, I32, I32, I32, I32, F32, P, I64, P, I32, P]),
+    "vdk_wa_cos_fwd_workspace_bytes": (C.c_int, [I32, I32, PSZ]),
+    "vdk_wa_cos_fwd": (C.c_int, [P, I64, P, I64, P, P, P, P, I32, I64, I32, P, I32, P, SZ, P]),
+    "vdk_wa_cos_bwd_workspace_bytes": (C.c_int, [I64, I32, I32, PSZ]),
+    "vdk_wa_cos_bwd": (C.c_int, [P, I64, P, P, I64, P, P, P, P, I32, I64, I32, P, P, I64, P, P, I32, P, SZ, P]),
 }
 
 

@@ -43,6 +43,17 @@ int vdk_attn_pool_fwd_hd(const float* q, const void* kv, int64_t ldkv, int32_t B
                          int32_t dtype, void* stream);
 int vdk_attn_pool_bwd_hd(const float* q, const void* kv, int64_t ldkv, const float* probs, const float* dout, int64_t lddo, int32_t B, int32_t N, int32_t H, int32_t head_dim,
                          float scale, void* dkv, int64_t lddkv, float* dq_part, int32_t dtype, void* stream);
+/* SwinV2 cosine window attention (csrc/window_attention_cos.hip): 64-token windows (8 x 8), head dim 32.  qkv 16-bit [windows * 64, ld] (q | k | v thirds of 3 * H * 32 columns),
+ * ld >= 3 * H * 32; o / dout [windows * 64, ldo]; lse f32 [windows, H, 64] (fwd: may be NULL); tau f32 [H] = exp(min(logit_scale, ln 100)), formed by the caller; bias f32
+ * [H, 64, 64]; mask f32 [nW, 64, 64] or NULL (window w takes mask[w mod nW], windows % nW == 0); rowidx int32 [windows * 64] or NULL: token j of window w is row
+ * rowidx[w * 64 + j] of qkv / o / dout / dqkv; opf 0 = bf16, 1 = fp16.  bwd: dqkv [windows * 64, ldd] (dq | dk | dv), dbias f32 [H, 64, 64] and dtau f32 [H], both summed
+ * over every window and overwritten.  Pointers (the workspace included) 16-byte aligned, pitches multiples of 8.  ws: the *_workspace_bytes of the same call. */
+int vdk_wa_cos_fwd_workspace_bytes(int32_t nW, int32_t H, size_t* bytes);
+int vdk_wa_cos_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, const float* tau, const float* bias, const float* mask, int32_t nW, int64_t windows, int32_t H,
+                   const int32_t* rowidx, int32_t opf, void* ws, size_t ws_bytes, void* stream);
+int vdk_wa_cos_bwd_workspace_bytes(int64_t windows, int32_t nW, int32_t H, size_t* bytes);
+int vdk_wa_cos_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, const float* tau, const float* bias, const float* mask, int32_t nW,
+                   int64_t windows, int32_t H, const int32_t* rowidx, void* dqkv, int64_t ldd, float* dbias, float* dtau, int32_t opf, void* ws, size_t ws_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _abi, _lib, convnext, heads, ops, resnet, swin, vit
+from . import _abi, _lib, convnext, heads, ops, resnet, swin, swinv2, vit
 
 
 def _up(x, a):
@@ -205,6 +205,10 @@ class _NeckCNNFn(torch.autograd.Function):
         return dx.view(B, Hh, Ww, Cc).permute(0, 3, 1, 2), dbn2_w, dbn2_b, dlin_w.contiguous(), dlin_b, dbn_w, dbn_b, None
 
 
+_SWINV2_NEEDS_ENGINE = ("{what} needs a native engine; SwinV2 (swinv2_*_window8_256) is served as autograd nodes over the kernels and trains under a plain torch "
+                        "optimizer over model.parameters() (with a loss scale for fp16 operands).  The native vdk_swinv2_* engine and its fused train step are a follow-up.")
+
+
 class TimmWrapper(nn.Module):
     """models/faceX/backbone/timm_wrapper.py: timm backbone without head/pool + embedding neck -> [B, feat_dim]."""
 
@@ -238,14 +242,24 @@ class TimmWrapper(nn.Module):
             self.is_cnn = True
             hw, channels = image_size // 32, self.model.num_features
             self.output_layer = nn.Sequential(nn.BatchNorm2d(hw), nn.Flatten(1), nn.Linear(hw * hw * channels, feat_dim), nn.BatchNorm1d(feat_dim)).to(dev)
+        elif model_name in swinv2.TIMM_SWINV2S:
+            # SwinV2 window8_256: the same NHWC map read as NCHW, [B, 8, 8, C] at 256 x 256 -> BatchNorm2d(8), Flatten, Linear(8 * 8 * C, feat_dim), BatchNorm1d.  The
+            # backbone is the autograd-node form (no native engine yet): it trains under a torch optimizer, FaceTrainStep and forward_precise refuse it.
+            self.model = swinv2.create_model(model_name, pretrained=False, num_classes=0, img_size=image_size, device=dev, backend=self.be, operand=operand)
+            self.is_cnn = True
+            hw, channels = image_size // 32, self.model.num_features
+            self.output_layer = nn.Sequential(nn.BatchNorm2d(hw), nn.Flatten(1), nn.Linear(hw * hw * channels, feat_dim), nn.BatchNorm1d(feat_dim)).to(dev)
         else:
-            raise NotImplementedError(f"backbone '{model_name}': the HIP engines cover {sorted(vit.TIMM_VITS)}, {sorted(convnext.TIMM_CONVNEXTS)} and {sorted(swin.TIMM_SWINS)}")
+            raise NotImplementedError(f"backbone '{model_name}': the HIP engines cover {sorted(vit.TIMM_VITS)}, {sorted(convnext.TIMM_CONVNEXTS)} and {sorted(swin.TIMM_SWINS)}"
+                                      f"; as autograd nodes over the kernels: {sorted(swinv2.TIMM_SWINV2S)}")
 
     @torch.no_grad()
     def forward_precise(self, x):
         """Evaluation embedding with fp32 activations and fp32-MFMA contractions end to end (backbone + neck in eval mode): agrees with the reference's
         PyTorch-CPU fp32 embedding to ~1e-6, so downstream cosine top-k lists match the reference's.  Used by FeatureExtractor(precise=True)."""
         be, ol = self.be, self.output_layer
+        if isinstance(self.model, swinv2.SwinTransformerV2):
+            raise NotImplementedError(_SWINV2_NEEDS_ENGINE.format(what="forward_precise (fp32-MFMA evaluation)"))
         if not hasattr(self.model, "forward_precise"):
             raise NotImplementedError("forward_precise (fp32-MFMA evaluation) is built for the native ViT, ConvNeXt and Swin engines; this backbone object has none")
         feat = self.model.forward_precise(x)
@@ -407,7 +421,8 @@ class VisionWrapper:
         arch = name[5:].split(".")[0]
         # timm-resnet18 | timm-convnext_* (pet.yaml:21-22) | timm-vit_*
         factory = (resnet.create_model if arch in resnet.TIMM_RESNETS else convnext.create_model if arch in convnext.TIMM_CONVNEXTS else
-                   swin.create_model if arch in swin.TIMM_SWINS else vit.create_model)      # timm-swin_base_patch4_window7_224 is pet.yaml:25's default
+                   swin.create_model if arch in swin.TIMM_SWINS else swinv2.create_model if arch.startswith("swinv2_") else vit.create_model)      # timm-swin_base_patch4_window7_224 is pet.yaml:25's default; every
+        #                                                                                     swinv2_ id goes to swinv2.create_model, whose KeyError lists the served window-8 ids
         self.model = factory(arch, pretrained=False, num_classes=model_cfg["num_classes"], img_size=model_cfg.get("image_size") or 224, device=device,
                              backend=backend, **kwargs)
         if not model_cfg.get("pretrained", False):
@@ -465,6 +480,8 @@ class FaceTrainStep:
         self.bb = model.trainingwrapper["backbone"]
         if precision == "fp32" and shard_head:
             raise NotImplementedError("precision='fp32' with a class-sharded head is not built")
+        if isinstance(self.bb.model, swinv2.SwinTransformerV2):
+            raise NotImplementedError(_SWINV2_NEEDS_ENGINE.format(what="FaceTrainStep"))
         if not hasattr(self.bb.model, "engine"):
             raise NotImplementedError("FaceTrainStep needs a backbone with a native engine (ViT, ConvNeXt, Swin with native=True); the autograd-node Swin trains under "
                                       "the reference's own Trainer (torch optimizer over model.parameters())")

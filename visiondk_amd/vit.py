@@ -629,6 +629,10 @@ class FusedTrainStep:
                  label_smoothing: float = 0.0, max_norm: float = 10.0, ema: bool = True, comm=None, sam: bool = False,
                  sam_rho: float = 0.05, sam_adaptive: bool = True, init_scale: float = 65536.0):
         self.model = model
+        from . import swinv2                     # (here: swinv2 imports swin, which imports this module's names lazily as well)
+        if isinstance(model, swinv2.SwinTransformerV2):
+            raise NotImplementedError("FusedTrainStep needs a native engine; SwinV2 (swinv2_*_window8_256) is served as autograd nodes over the kernels and trains under a plain "
+                                      "torch optimizer over model.parameters() (with a loss scale for fp16 operands).  The native vdk_swinv2_* engine is a follow-up.")
         self.eng = model.engine
         self.be = self.eng.be
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
