@@ -15,9 +15,9 @@ from dataclasses import dataclass
 from typing import Callable, Optional, Tuple
 
 import torch
-import torch.nn as nn
 
 from . import _abi, _lib
+from ._engine import FlatEngine, FlatParamModule, seeded_generator
 
 
 @dataclass(frozen=True)
@@ -39,7 +39,7 @@ TIMM_CONVNEXTS = {
 }
 
 
-class ConvNeXtEngine:
+class ConvNeXtEngine(FlatEngine):
     """Owns the flat HBM buffers (fp32 master params, bf16 / derived operand copies, grads, workspace); calls vdk_convnext_*."""
 
     def __init__(self, spec: ConvNeXtSpec, device=None, backend: Optional[_lib.Backend] = None, operand: str = "bf16"):
@@ -48,42 +48,24 @@ class ConvNeXtEngine:
         the train steps then run GradScaler's protocol (loss scale into the output gradient, un-scale + inf check in the optimizer kernel)."""
         if operand not in ("bf16", "fp16"):
             raise ValueError("operand must be 'bf16' or 'fp16'")
-        self.spec = spec
-        self.operand = operand
-        self.dt16 = torch.float16 if operand == "fp16" else torch.bfloat16
-        self.be = backend or _lib.load()
-        self.device = torch.device(device if device is not None else ("cuda" if self.be.device_only else "cpu"))
+        super().__init__(spec, device, backend, operand)
+        self.dt16 = self.op_dtype
         cfg = self._cfg(1)
         nf, nt, wx = _abi.I64(0), _abi.I32(0), C.c_size_t(0)
         self.be.check(self.be.lib.vdk_convnext_param_count(C.byref(cfg), C.byref(nf), C.byref(nt), C.byref(wx)), "vdk_convnext_param_count")
         self.n_floats, self.n_tensors = nf.value, nt.value
-        self.entries = []
-        name = C.create_string_buffer(96)
-        off, numel, ndim = _abi.I64(0), _abi.I64(0), _abi.I32(0)
-        shape = (_abi.I64 * 4)()
-        for i in range(self.n_tensors):
-            self.be.check(self.be.lib.vdk_convnext_param_info(C.byref(cfg), i, name, 96, C.byref(off), C.byref(numel), shape, C.byref(ndim)),
-                          "vdk_convnext_param_info")
-            self.entries.append((name.value.decode(), off.value, numel.value, tuple(shape[j] for j in range(ndim.value))))
-        dev = self.device
-        self.params = torch.zeros(self.n_floats, dtype=torch.float32, device=dev)
-        self.grads = torch.zeros(self.n_floats, dtype=torch.float32, device=dev)
-        self.wb16 = torch.zeros(self.n_floats, dtype=self.dt16, device=dev)
-        self.wx = torch.zeros(wx.value, dtype=torch.uint8, device=dev)
+        self.entries = self._read_entries(self.be.lib.vdk_convnext_param_info, cfg, self.n_tensors)
+        # buffers: no BatchNorm, nothing to broadcast (the train step shared with the ResNet engine asks)
+        self._alloc(wx=(wx.value, torch.uint8), buffers=(0, torch.float32))
         self.out_hw = spec.img_size // 32
         self.out_ch = spec.dims[3]
         self.cp = (spec.num_classes + 7) // 8 * 8          # logits row stride in classifier mode
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_batch = -1
         self._ws_img = spec.img_size
         self._out: Optional[torch.Tensor] = None
-        self._weights_version = None
-        self.buffers = torch.zeros(0, dtype=torch.float32, device=dev)      # no BatchNorm: nothing to broadcast (the train step shared with the ResNet engine asks)
         # "bf16": bf16 MFMA operands, fp32 accumulation / residual stream / master weights (the reference's autocast arithmetic, classifier loop).
         # "fp32": forward() / backward() run vdk_convnext_forward_train_f32 / vdk_convnext_backward_train_f32 -- fp32 activations, every contraction on the fp32 MFMA: the
         # arithmetic of the reference's face / CBIR loop, which has no autocast (engine/procedure/train.py:217-227).  Feature mode only.
         self.precision = "bf16"
-        self._ws_t32: Optional[torch.Tensor] = None
 
     def _cfg(self, batch: int, img: Optional[int] = None) -> _abi.ConvNextConfig:
         s = self.spec
@@ -95,14 +77,9 @@ class ConvNeXtEngine:
         (engine/vision_engine.py:181-222) changes the input resolution between epochs; feature mode stays at spec.img_size (the neck's Linear fixes it)"""
         img = img or self.spec.img_size
         if self._ws is None or self._ws_batch != batch or self._ws_img != img:
-            need = C.c_size_t(0)
-            cfg = self._cfg(batch, img)
             self._ws_img = img
             self.out_hw = img // 32
-            self.be.check(self.be.lib.vdk_convnext_workspace_bytes(C.byref(cfg), C.byref(need)), "vdk_convnext_workspace_bytes")
-            if self._ws is None or self._ws.numel() < need.value:      # grow-only (OHEM: a different batch size every iteration)
-                self._ws = None
-                self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            self._grow("_ws", self.be.lib.vdk_convnext_workspace_bytes, self._cfg(batch, img))
             self._ws_batch = batch
             if self.spec.num_classes > 0:
                 self._out = torch.empty((batch, self.cp), dtype=torch.float32, device=self.device)
@@ -116,10 +93,6 @@ class ConvNeXtEngine:
         be.check(be.lib.vdk_convnext_refresh_weights(C.byref(cfg), be.ptr(self.params), be.ptr(self.wb16), be.ptr(self.wx), int(skip_wb16), be.stream()),
                  "vdk_convnext_refresh_weights")
         self._weights_version = self.params._version
-
-    def _ensure_fresh(self) -> None:
-        if self._weights_version != self.params._version:
-            self.refresh_weights()
 
     def dlogits_rows(self, batch: int) -> int:
         """rows of the 16-bit dlogits buffer backward() expects in classifier mode (the fc weight gradient contracts over 64-row K tiles)"""
@@ -156,11 +129,7 @@ class ConvNeXtEngine:
         be = self.be
         cfg = self._cfg(B)
         if self._ws_t32 is None or self._ws_batch != B:
-            need = C.c_size_t(0)
-            be.check(be.lib.vdk_convnext_train_f32_workspace_bytes(C.byref(cfg), C.byref(need)), "vdk_convnext_train_f32_workspace_bytes")
-            if self._ws_t32 is None or self._ws_t32.numel() < need.value:
-                self._ws_t32 = None
-                self._ws_t32 = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            self._grow("_ws_t32", be.lib.vdk_convnext_train_f32_workspace_bytes, cfg)
             self._ws_batch, self._ws_img = B, self.spec.img_size
             self._out = torch.empty((B * self.out_hw * self.out_hw, self.out_ch), dtype=torch.float32, device=self.device)
         self._ensure_fresh()                      # the tap-major depthwise weights live in wx
@@ -170,23 +139,17 @@ class ConvNeXtEngine:
 
     def forward_precise(self, x: torch.Tensor) -> torch.Tensor:
         """Evaluation forward with fp32 activations and fp32-MFMA contractions (vdk_convnext_forward_f32) -> f32 [B*h*w, C] NHWC rows"""
-        s = self.spec
-        if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (s.in_chans, s.img_size, s.img_size):
-            raise ValueError(f"expected float32 [B, {s.in_chans}, {s.img_size}, {s.img_size}], got {tuple(x.shape)} {x.dtype}")
-        if s.num_classes > 0:
+        x = self._image(x)
+        if self.spec.num_classes > 0:
             raise NotImplementedError("the fp32-MFMA evaluation forward is built for feature mode (embeddings); classifier logits use forward()")
-        x = x.contiguous()
         B = x.shape[0]
         self._ensure_fresh()                      # the tap-major depthwise weights live in wx
         cfg = self._cfg(B)
         be = self.be
-        need = C.c_size_t(0)
-        be.check(be.lib.vdk_convnext_workspace_f32_bytes(C.byref(cfg), C.byref(need)), "vdk_convnext_workspace_f32_bytes")
-        if getattr(self, "_ws32", None) is None or self._ws32.numel() < need.value:
-            self._ws32 = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        ws = self._grow("_ws32", be.lib.vdk_convnext_workspace_f32_bytes, cfg)
         out = torch.empty((B * self.out_hw * self.out_hw, self.out_ch), dtype=torch.float32, device=self.device)
-        be.check(be.lib.vdk_convnext_forward_f32(C.byref(cfg), be.ptr(x), be.ptr(self.params), be.ptr(self.wx), be.ptr(self._ws32), self._ws32.numel(),
-                                                 be.ptr(out), be.stream()), "vdk_convnext_forward_f32")
+        be.check(be.lib.vdk_convnext_forward_f32(C.byref(cfg), be.ptr(x), be.ptr(self.params), be.ptr(self.wx), be.ptr(ws), ws.numel(), be.ptr(out), be.stream()),
+                 "vdk_convnext_forward_f32")
         return out
 
     def backward(self, dout: torch.Tensor, on_ready: Optional[Callable[[int, int], None]] = None, sync_group=False) -> torch.Tensor:
@@ -232,17 +195,14 @@ class _ConvNeXtFunction(torch.autograd.Function):
             d[:B, :n] = dout.to(eng.dt16)
         else:
             d = dout.permute(0, 2, 3, 1).contiguous().view(-1, eng.out_ch)
-        g = eng.backward(d)
-        return (None, None) + tuple(g[off:off + numel].view(shape) for (_, off, numel, shape) in eng.entries)
+        return ctx.module._flat_grads(eng.backward(d))
 
 
-class _Holder(nn.Module):
-    """empty container mirroring one level of timm's module tree; owns Parameters only"""
-
-
-class ConvNeXt(nn.Module):
+class ConvNeXt(FlatParamModule):
     """Drop-in for `timm.create_model('convnext_*', pretrained=False, num_classes=0, global_pool='')` (feature mode, TimmWrapper) and for
     `timm.create_model('convnext_*', num_classes=N)` (classifier: head = global average pool -> head.norm -> head.fc, VisionWrapper)."""
+
+    family = "ConvNeXt"
 
     def __init__(self, spec: ConvNeXtSpec, device=None, backend: Optional[_lib.Backend] = None, seed: Optional[int] = None, operand: str = "bf16"):
         super().__init__()
@@ -250,25 +210,13 @@ class ConvNeXt(nn.Module):
         self.engine = ConvNeXtEngine(spec, device=device, backend=backend, operand=operand)
         self.num_classes = spec.num_classes
         self.num_features = spec.dims[3]
-        self._plist = []
-        for name, off, numel, shape in self.engine.entries:
-            p = nn.Parameter(self.engine.params[off:off + numel].view(shape))
-            parts = name.split(".")
-            m = self
-            for part in parts[:-1]:
-                if part not in m._modules:
-                    m.add_module(part, _Holder())
-                m = m._modules[part]
-            m.register_parameter(parts[-1], p)
-            self._plist.append((name, p))
+        self._build_tree()
         self.reset_parameters(seed)
 
     def reset_parameters(self, seed: Optional[int] = None) -> None:
         """timm's own init (trunc_normal .02 Conv/Linear weights, zero biases, LayerNorm (1,0), layer scale 1e-6): the reference's
         FaceTrainingWrapper.reset_parameters is defined but never called."""
-        gen = torch.Generator(device="cpu")
-        # no explicit seed: drawn from torch's global generator, so torch.manual_seed(s) reproduces the initialisation as it does for the reference's model
-        gen.manual_seed(seed if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
+        gen = seeded_generator(seed)
         with torch.no_grad():
             for name, p in self._plist:
                 if name.endswith(".gamma"):
@@ -282,31 +230,6 @@ class ConvNeXt(nn.Module):
                 else:
                     v = torch.empty(p.shape).normal_(0, 0.02, generator=gen).clamp_(-2.0, 2.0)
                 p.copy_(v.to(p.device))
-
-    def _sync_flat(self) -> None:
-        eng = self.engine
-        base = eng.params.data_ptr()
-        for (name, off, numel, shape), (_, p) in zip(eng.entries, self._plist):
-            if p.data_ptr() != base + off * 4:
-                with torch.no_grad():
-                    eng.params[off:off + numel].view(shape).copy_(p.detach().to(eng.device))
-                    p.data = eng.params[off:off + numel].view(shape)
-
-    def _apply(self, fn, recurse=True):
-        probe = fn(torch.zeros(1, dtype=torch.float32, device=self.engine.device))
-        if probe.device != self.engine.device or probe.dtype != torch.float32:
-            if probe.dtype != torch.float32:
-                raise RuntimeError("visiondk_amd ConvNeXt keeps fp32 master weights; bf16 copies are internal")
-            if self.engine.be.device_only and probe.device.type != "cuda":
-                raise RuntimeError("visiondk_amd ConvNeXt lives on the GPU (no CPU fallback)")
-            eng = self.engine
-            eng.device = probe.device
-            for attr in ("params", "grads", "wb16", "wx"):
-                setattr(eng, attr, getattr(eng, attr).to(probe.device))
-            eng._ws, eng._ws_batch, eng._weights_version = None, -1, None
-            for (name, off, numel, shape), (_, p) in zip(eng.entries, self._plist):
-                p.data = eng.params[off:off + numel].view(shape)
-        return self
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return _ConvNeXtFunction.apply(x, self, *[p for _, p in self._plist])

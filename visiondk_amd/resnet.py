@@ -11,9 +11,9 @@ from dataclasses import dataclass
 from typing import Callable, Optional, Tuple
 
 import torch
-import torch.nn as nn
 
 from . import _abi, _lib
+from ._engine import FlatEngine, FlatParamModule, pad_cast_dlogits, seeded_generator
 
 
 @dataclass(frozen=True)
@@ -39,44 +39,20 @@ TIMM_RESNETS = {
 }
 
 
-class ResNetEngine:
+class ResNetEngine(FlatEngine):
     def __init__(self, spec: ResNetSpec, device=None, backend: Optional[_lib.Backend] = None, operand: str = "bf16"):
         # operand: the 16-bit format of every convolution / fc operand, saved activation and gradient operand -- "bf16", or "fp16" = what the reference's
         # `torch.autocast(device_type=...)` (engine/procedure/train.py:118, no dtype => float16 on a GPU) computes in, with GradScaler's loss scale around the backward
-        assert operand in ("bf16", "fp16"), operand
-        self.spec = spec
-        self.operand = operand
-        self.op_dtype = torch.float16 if operand == "fp16" else torch.bfloat16
-        self.be = backend or _lib.load()
-        self.device = torch.device(device if device is not None else ("cuda" if self.be.device_only else "cpu"))
+        super().__init__(spec, device, backend, operand)
         cfg = self._cfg(1)
         nf, nt, nbf, nb, wx = _abi.I64(0), _abi.I32(0), _abi.I64(0), _abi.I32(0), C.c_size_t(0)
         self.be.check(self.be.lib.vdk_resnet_param_count(C.byref(cfg), C.byref(nf), C.byref(nt), C.byref(nbf), C.byref(nb), C.byref(wx)), "vdk_resnet_param_count")
         self.n_floats = nf.value
-        name = C.create_string_buffer(96)
-        off, numel, ndim = _abi.I64(0), _abi.I64(0), _abi.I32(0)
-        shape = (_abi.I64 * 4)()
-
-        def entries(which, n):
-            out = []
-            for i in range(n):
-                self.be.check(self.be.lib.vdk_resnet_param_info(C.byref(cfg), which, i, name, 96, C.byref(off), C.byref(numel), shape, C.byref(ndim)),
-                              "vdk_resnet_param_info")
-                out.append((name.value.decode(), off.value, numel.value, tuple(shape[j] for j in range(ndim.value))))
-            return out
-        self.entries = entries(0, nt.value)
-        self.buffer_entries = entries(1, nb.value)
-        dev = self.device
-        self.params = torch.zeros(nf.value, dtype=torch.float32, device=dev)
-        self.grads = torch.zeros(nf.value, dtype=torch.float32, device=dev)
-        self.buffers = torch.zeros(nbf.value, dtype=torch.float32, device=dev)
-        self.wb16 = torch.zeros(nf.value, dtype=self.op_dtype, device=dev)
-        self.wx = torch.zeros(wx.value, dtype=torch.uint8, device=dev)
+        self.entries = self._read_entries(self.be.lib.vdk_resnet_param_info, cfg, nt.value, 0)
+        self.buffer_entries = self._read_entries(self.be.lib.vdk_resnet_param_info, cfg, nb.value, 1)       # the BatchNorm running statistics, inside `buffers`
+        self._alloc(buffers=(nbf.value, torch.float32), wx=(wx.value, torch.uint8))
         self.cp = (spec.num_classes + 7) // 8 * 8
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_batch = -1
         self._logits: Optional[torch.Tensor] = None
-        self._weights_version = None
 
     def _cfg(self, batch: int, img: Optional[int] = None, bn_momentum: Optional[float] = None) -> _abi.ResNetConfig:
         s = self.spec
@@ -88,12 +64,7 @@ class ResNetEngine:
         """keyed on (batch, image size): the reference's progressive resizing (engine/vision_engine.py:181-222) changes the input resolution between
         epochs; a fully convolutional network with a global pool takes any multiple of 32"""
         if self._ws is None or self._ws_batch != (batch, img):
-            need = C.c_size_t(0)
-            cfg = self._cfg(batch, img)
-            self.be.check(self.be.lib.vdk_resnet_workspace_bytes(C.byref(cfg), C.byref(need)), "vdk_resnet_workspace_bytes")
-            if self._ws is None or self._ws.numel() < need.value:      # grow-only (OHEM: a different batch size every iteration)
-                self._ws = None
-                self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            self._grow("_ws", self.be.lib.vdk_resnet_workspace_bytes, self._cfg(batch, img))
             self._ws_batch = (batch, img)
             self._logits = torch.empty((batch, self.cp), dtype=torch.float32, device=self.device)
         return self._ws
@@ -125,8 +96,7 @@ class ResNetEngine:
         x = x.contiguous()
         B, img = x.shape[0], x.shape[2]
         ws = self._workspace(B, img)
-        if self._weights_version != self.params._version:
-            self.refresh_weights()
+        self._ensure_fresh()
         cfg = self._cfg(B, img, bn_momentum)
         be = self.be
         cb = self._sync_cb(sync_group)
@@ -157,23 +127,13 @@ class _ResNetFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits):
         eng = ctx.module.engine
-        be = eng.be
-        B, Cn = dlogits.shape
-        stage = torch.zeros((B, eng.cp), dtype=torch.float32, device=dlogits.device)
-        stage[:, :Cn].copy_(dlogits)
-        dl = torch.empty((B, eng.cp), dtype=eng.op_dtype, device=dlogits.device)
-        cast = be.lib.vdk_cast_f32_f16 if eng.operand == "fp16" else be.lib.vdk_cast_f32_bf16      # (fp16: the incoming gradient carries GradScaler's loss scale, train.py:205)
-        be.check(cast(be.ptr(stage), be.ptr(dl), stage.numel(), be.stream()), "vdk_cast_f32_16")
-        g = eng.backward(dl)
-        return (None, None) + tuple(g[off:off + numel].view(shape) for (_, off, numel, shape) in eng.entries)
+        return ctx.module._flat_grads(eng.backward(pad_cast_dlogits(eng, dlogits)))
 
 
-class _Holder(nn.Module):
-    """empty container mirroring one level of timm's module tree; owns Parameters / buffers only"""
-
-
-class ResNet(nn.Module):
+class ResNet(FlatParamModule):
     """Drop-in for `timm.create_model('resnet18' | 'resnet34', pretrained=False, num_classes=C)`."""
+
+    family = "ResNet"
 
     def __init__(self, spec: ResNetSpec, device=None, backend: Optional[_lib.Backend] = None, seed: Optional[int] = None, operand: str = "bf16"):
         super().__init__()
@@ -181,36 +141,23 @@ class ResNet(nn.Module):
         self.engine = ResNetEngine(spec, device=device, backend=backend, operand=operand)
         self.num_classes = spec.num_classes
         eng = self.engine
-        self._plist, self._blist = [], []
+        self._build_tree()
+        self._blist = []
         bufs = {n: (off, numel, shape) for n, off, numel, shape in eng.buffer_entries}
-
-        def holder(path):
-            m = self
-            for part in path:
-                if part not in m._modules:
-                    m.add_module(part, _Holder())
-                m = m._modules[part]
-            return m
-        for name, off, numel, shape in eng.entries:
-            parts = name.split(".")
-            m = holder(parts[:-1])
-            p = nn.Parameter(eng.params[off:off + numel].view(shape))
-            m.register_parameter(parts[-1], p)
-            self._plist.append((name, p))
-            if parts[-1] == "bias" and ".".join(parts[:-1]) + ".running_mean" in bufs:      # a BatchNorm: its buffers follow weight / bias, like nn.BatchNorm2d
+        for name, _ in self._plist:
+            bn_name, _, leaf = name.rpartition(".")
+            if leaf == "bias" and bn_name + ".running_mean" in bufs:      # a BatchNorm: its buffers are views of the engine's, named like nn.BatchNorm2d's
+                m = self._holder(bn_name.split("."))
                 for bn in ("running_mean", "running_var"):
-                    boff, bnum, bshape = bufs[".".join(parts[:-1]) + "." + bn]
-                    t = eng.buffers[boff:boff + bnum].view(bshape)
-                    m.register_buffer(bn, t)
-                    self._blist.append((".".join(parts[:-1]) + "." + bn, boff, bnum, bshape, m, bn))
+                    boff, bnum, bshape = bufs[bn_name + "." + bn]
+                    m.register_buffer(bn, eng.buffers[boff:boff + bnum].view(bshape))
+                    self._blist.append((bn_name + "." + bn, boff, bnum, bshape, m, bn))
                 m.register_buffer("num_batches_tracked", torch.zeros((), dtype=torch.long, device=eng.device))
         self.reset_parameters(seed)
 
     def reset_parameters(self, seed: Optional[int] = None) -> None:
         """the reference's re-init (classify_model.py:70-81): N(0, .02) Conv / Linear weights, zero Linear bias, BatchNorm (1, 0); running stats (0, 1)"""
-        gen = torch.Generator(device="cpu")
-        # no explicit seed: drawn from torch's global generator, so torch.manual_seed(s) reproduces the initialisation as it does for the reference's model
-        gen.manual_seed(seed if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
+        gen = seeded_generator(seed)
         with torch.no_grad():
             for name, p in self._plist:
                 if name.endswith(".bias"):
@@ -224,13 +171,8 @@ class ResNet(nn.Module):
                 getattr(m, bn).fill_(1.0 if bn == "running_var" else 0.0)
 
     def _sync_flat(self) -> None:
+        super()._sync_flat()
         eng = self.engine
-        base = eng.params.data_ptr()
-        for (name, off, numel, shape), (_, p) in zip(eng.entries, self._plist):
-            if p.data_ptr() != base + off * 4:
-                with torch.no_grad():
-                    eng.params[off:off + numel].view(shape).copy_(p.detach().to(eng.device))
-                    p.data = eng.params[off:off + numel].view(shape)
         bbase = eng.buffers.data_ptr()
         for name, off, numel, shape, m, bn in self._blist:
             t = getattr(m, bn)
@@ -240,22 +182,13 @@ class ResNet(nn.Module):
                     m._buffers[bn] = eng.buffers[off:off + numel].view(shape)
 
     def _apply(self, fn, recurse=True):
-        probe = fn(torch.zeros(1, dtype=torch.float32, device=self.engine.device))
-        if probe.device != self.engine.device or probe.dtype != torch.float32:
-            if probe.dtype != torch.float32:
-                raise RuntimeError("visiondk_amd ResNet keeps fp32 master weights; bf16 copies are internal")
-            if self.engine.be.device_only and probe.device.type != "cuda":
-                raise RuntimeError("visiondk_amd ResNet lives on the GPU (no CPU fallback)")
-            eng = self.engine
-            eng.device = probe.device
-            for attr in ("params", "grads", "buffers", "wb16", "wx"):
-                setattr(eng, attr, getattr(eng, attr).to(probe.device))
-            eng._ws, eng._ws_batch, eng._weights_version = None, -1, None
-            for (name, off, numel, shape), (_, p) in zip(eng.entries, self._plist):
-                p.data = eng.params[off:off + numel].view(shape)
+        eng = self.engine
+        before = eng.device
+        super()._apply(fn, recurse)
+        if eng.device != before:      # the engine moved, its buffers with it
             for name, off, numel, shape, m, bn in self._blist:
                 m._buffers[bn] = eng.buffers[off:off + numel].view(shape)
-                m._buffers["num_batches_tracked"] = m._buffers["num_batches_tracked"].to(probe.device)
+                m._buffers["num_batches_tracked"] = m._buffers["num_batches_tracked"].to(eng.device)
         return self
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

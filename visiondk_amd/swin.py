@@ -24,11 +24,13 @@ from typing import Optional, Sequence
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
-from ._abi import ACT_DGELU, ACT_GELU
+from . import _abi, _lib, ops
+from ._engine import OPERANDS, FlatEngine, FlatParamModule, _Holder, check_image, pad_cast_dlogits, seeded_generator
+from ._nodes import _BiasGather, _cast, _LinearFn, _Lin, _LN, _LNRes, _Mlp, _Pool
 
 WS = 7
 N = WS * WS
+BF = torch.bfloat16      # SwinTransformerAutograd's operand format (fp16 is the native engine's)
 
 
 @dataclass(frozen=True)
@@ -77,131 +79,50 @@ def _shift_mask(H: int, W: int, ws: int, shift: int) -> torch.Tensor:
     return m.masked_fill(m != 0, -100.0).masked_fill(m == 0, 0.0).contiguous()
 
 
-def _wgrad(be, dyb: torch.Tensor, xb: torch.Tensor) -> torch.Tensor:
-    """dW f32 [N, K] = dY^T X for bf16 dY [T, N], X [T, K]: the TN GEMM straight from both tensors when T % 64 == 0, else through zero-padded transposes"""
-    T, Nn = dyb.shape
-    K = xb.shape[1]
-    if T % 64 == 0 and Nn % 8 == 0 and K % 8 == 0:
-        tiles = ((Nn + 255) // 256) * ((K + 255) // 256)
-        sk = max(1, min(256 // tiles, (T // 64) // 4, 64))
-        return ops.gemm_nt(dyb, xb, out_dtype=torch.float32, trans=True, splitk=sk, backend=be)
-    dyt = ops.transpose_pad(dyb, backend=be)                    # [N, Tp]
-    xt = ops.transpose_pad(xb, backend=be)                      # [K, Tp]
-    return ops.gemm_nt(dyt, xt, out_dtype=torch.float32, backend=be)
+def _uses_table(idx: torch.Tensor, ws: int) -> torch.Tensor:
+    """for the bias gather's backward: where each of the (2 ws - 1)^2 table entries is used in the relative-position index, int32 [(2 ws - 1)^2, ws^2] (-1 padded)"""
+    R = (2 * ws - 1) ** 2
+    uses = torch.full((R, ws * ws), -1, dtype=torch.int32)
+    flat = idx.view(-1)
+    for r in range(R):
+        pos = (flat == r).nonzero().view(-1)
+        uses[r, :pos.numel()] = pos.to(torch.int32)
+    return uses
 
 
-def _bf(be, t: torch.Tensor) -> torch.Tensor:
-    return t if t.dtype == torch.bfloat16 else ops.cast_bf16(t.contiguous(), backend=be)
+def _window_rows(res: int, shift: int, ws: int, B: int) -> torch.Tensor:
+    """the image-order row of every (window, token) of the (cyclically shifted) window partition of a batch of B res x res maps, int32"""
+    idx = torch.arange(B * res * res).view(B, res, res, 1)
+    if shift:
+        idx = torch.roll(idx, (-shift, -shift), (1, 2))
+    return _partition(idx, ws).view(-1).to(torch.int32)
 
 
-# ---- autograd nodes over the kernels ----------------------------------------------------------------------------------------------------------
-class _LN(torch.autograd.Function):
-    """LayerNorm over the last dimension of f32 rows -> bf16 (a GEMM operand) or f32 (the residual stream)"""
-
-    @staticmethod
-    def forward(ctx, x, w, b, eps, out_dtype, be):
-        x2 = x.contiguous().view(-1, w.numel())
-        y, mean, rstd = ops.layernorm_fwd(x2, w.detach(), b.detach(), eps, out_dtype, backend=be)
-        ctx.save_for_backward(x2, mean, rstd, w)
-        ctx.be, ctx.shape = be, x.shape
-        return y.view(x.shape)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x2, mean, rstd, w = ctx.saved_tensors
-        dy2 = dy.contiguous().view(x2.shape)
-        dx, _, dg, db = ops.layernorm_bwd(dy2, x2, mean, rstd, w.detach(), want_bf16=False, backend=ctx.be)
-        return dx.view(ctx.shape), dg, db, None, None, None
+def _merge2x2(x: torch.Tensor) -> torch.Tensor:
+    """patch merging's gather: [B, H, W, C] -> [B, H/2, W/2, 4C]"""
+    B, H, W, Cc = x.shape
+    return x.reshape(B, H // 2, 2, W // 2, 2, Cc).permute(0, 1, 3, 4, 2, 5).flatten(3)
 
 
-class _LNRes(torch.autograd.Function):
-    """(LayerNorm(x) as bf16, x): the block's pre-norm with the shortcut routed through the same node, so that the backward adds the shortcut's gradient inside the
-    LayerNorm backward kernel (its `dres` input) instead of an autograd accumulation pass over the f32 stream.  The f32 dx carries its bf16 copy (written by the same kernel)
-    as `_vdk_bf16`: the next consumer is a GEMM and takes it instead of casting (see _grad_bf16)."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, eps, be):
-        x2 = x.contiguous().view(-1, w.numel())
-        y, mean, rstd = ops.layernorm_fwd(x2, w.detach(), b.detach(), eps, torch.bfloat16, backend=be)
-        ctx.save_for_backward(x2, mean, rstd, w)
-        ctx.be, ctx.shape = be, x.shape
-        return y.view(x.shape), x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, dy, dres):
-        x2, mean, rstd, w = ctx.saved_tensors
-        dy2 = dy.contiguous().view(x2.shape)
-        dr = dres.contiguous().view(x2.shape) if dres is not None else None
-        dx, dxb, dg, db = ops.layernorm_bwd(dy2, x2, mean, rstd, w.detach(), dres=dr, want_bf16=True, backend=ctx.be)
-        dx = dx.view(ctx.shape)
-        dx._vdk_bf16 = (dxb, dx._version, dx.data_ptr())      # valid only while this very tensor reaches the consumer unmodified (see _grad_bf16)
-        return dx, dg, db, None, None
+def _stem_patches(x: torch.Tensor) -> torch.Tensor:
+    """the 4 x 4 / stride 4 convolution is a Linear over (c, ky, kx) patches: [B, C, S, S] -> [B (S/4)^2, 16 C] (the patch operand is an index permutation of the image)"""
+    B, Cin, S, _ = x.shape
+    g = S // 4
+    return x.reshape(B, Cin, g, 4, g, 4).permute(0, 2, 4, 1, 3, 5).reshape(B * g * g, Cin * 16)
 
 
-def _grad_bf16(be, dy: torch.Tensor, rows: int) -> torch.Tensor:
-    """the bf16 [rows, C] operand of a gradient: the copy its producer attached (_LNRes.backward), else a cast"""
-    c = getattr(dy, "_vdk_bf16", None)
-    # the attached copy is trusted only if the gradient is still the producer's tensor, untouched: an in-place accumulation (a second consumer of the activation, a
-    # tensor hook) bumps _version, a re-materialised sum has another data pointer -- then the copy is stale and the gradient is cast again
-    if c is not None and c[0].numel() == dy.numel() and c[1] == dy._version and c[2] == dy.data_ptr():
-        return c[0].view(rows, -1)
-    return _bf(be, dy.contiguous().view(rows, -1))
+def _init_conv_linear(model: nn.Module) -> None:
+    """the reference's override after timm's init (classify_model.py:70-81): N(0, 0.02) for every Conv2d / Linear weight, zeros for Linear bias"""
+    for m in model.modules():
+        if isinstance(m, nn.Conv2d):
+            nn.init.normal_(m.weight, mean=0, std=0.02)
+        elif isinstance(m, nn.Linear):
+            nn.init.normal_(m.weight, mean=0, std=0.02)
+            if m.bias is not None:
+                nn.init.zeros_(m.bias)
 
 
-class _Lin(torch.autograd.Function):
-    """y = x W^T (+ b) (+ residual): bf16 operands on the MFMA GEMM; y bf16, or f32 when it joins the residual stream"""
-
-    @staticmethod
-    def forward(ctx, x, w, b, residual, out_dtype, be):
-        xb = _bf(be, x.contiguous().view(-1, x.shape[-1]))
-        wb = ops.cast_bf16(w.detach().contiguous(), backend=be)
-        res = residual.contiguous().view(-1, w.shape[0]) if residual is not None else None
-        y = ops.gemm_nt(xb, wb, out_dtype=out_dtype, bias=b.detach() if b is not None else None, residual=res, backend=be)
-        ctx.save_for_backward(xb, w)
-        ctx.be, ctx.has_b, ctx.has_r, ctx.xshape, ctx.xdtype = be, b is not None, residual is not None, x.shape, x.dtype
-        return y.view(*x.shape[:-1], w.shape[0])
-
-    @staticmethod
-    def backward(ctx, dy):
-        xb, w = ctx.saved_tensors
-        be = ctx.be
-        dyb = _grad_bf16(be, dy, dy.numel() // w.shape[0])
-        wt = ops.transpose_cast(w.detach().contiguous(), backend=be)        # bf16 [in, out]: B operand of dX = dY W
-        dx = ops.gemm_nt(dyb, wt[:, :w.shape[0]] if wt.shape[1] != w.shape[0] else wt, out_dtype=torch.bfloat16 if ctx.xdtype == torch.bfloat16 else torch.float32, backend=be)
-        dw = _wgrad(be, dyb, xb)
-        db = ops.colsum_bf16(dyb, backend=be) if ctx.has_b else None
-        dres = dy if ctx.has_r else None
-        return dx.view(ctx.xshape), dw, db, dres, None, None
-
-
-class _Mlp(torch.autograd.Function):
-    """x + fc2(gelu(fc1(h))): fc1 with the GELU epilogue (pre-activation kept), fc2 with the residual epilogue; backward with the dGELU epilogue on the fc2 input-gradient GEMM"""
-
-    @staticmethod
-    def forward(ctx, h, w1, b1, w2, b2, x, be):
-        hb = h.contiguous().view(-1, h.shape[-1])
-        w1b = ops.cast_bf16(w1.detach().contiguous(), backend=be); w2b = ops.cast_bf16(w2.detach().contiguous(), backend=be)
-        u = torch.empty((hb.shape[0], w1.shape[0]), dtype=torch.bfloat16, device=h.device)
-        g = ops.gemm_nt(hb, w1b, bias=b1.detach(), act=ACT_GELU, aux=u, backend=be)
-        y = ops.gemm_nt(g, w2b, out_dtype=torch.float32, bias=b2.detach(), residual=x.contiguous().view(-1, w2.shape[0]), backend=be)
-        ctx.save_for_backward(hb, u, g, w1, w2)
-        ctx.be, ctx.shape = be, x.shape
-        return y.view(x.shape)
-
-    @staticmethod
-    def backward(ctx, dy):
-        hb, u, g, w1, w2 = ctx.saved_tensors
-        be = ctx.be
-        dyb = _grad_bf16(be, dy, dy.numel() // w2.shape[0])
-        w2t = ops.transpose_cast(w2.detach().contiguous(), backend=be)       # [4C, C]
-        du = ops.gemm_nt(dyb, w2t, act=ACT_DGELU, aux=u, backend=be)
-        dw2 = _wgrad(be, dyb, g); db2 = ops.colsum_bf16(dyb, backend=be)
-        w1t = ops.transpose_cast(w1.detach().contiguous(), backend=be)       # [C, 4C]
-        dh = ops.gemm_nt(du, w1t, backend=be)
-        dw1 = _wgrad(be, du, hb); db1 = ops.colsum_bf16(du, backend=be)
-        return dh.view(*ctx.shape[:-1], w1.shape[1]), dw1, db1, dw2, db2, dy, None
-
-
+# ---- autograd nodes over the kernels (the model-independent ones: _nodes.py) ---------------------------------------------------------------------
 class _WinAttn(torch.autograd.Function):
     """the attention step of timm's WindowAttention on bf16 qkv rows; rowidx (int32 [T], a permutation) = the tensor row of every (window, token): the cyclic shift and the
     window partition / reverse of the block as an index inside the kernels, so qkv and o stay in image order (None: rows already in (window, token) order)"""
@@ -216,11 +137,9 @@ class _WinAttn(torch.autograd.Function):
         biasc = bias.detach().contiguous()
         scale = (Cc // heads) ** -0.5
         nW = 0 if mask is None else mask.shape[0]
-        need = C.c_size_t(0)
-        be.check(be.lib.vdk_window_attention_fwd_workspace_bytes(nW, heads, C.byref(need)), "vdk_window_attention_fwd_workspace_bytes")
-        ws = torch.empty(need.value, dtype=torch.uint8, device=qkv.device)
+        ws, n = ops._ws(be, be.lib.vdk_window_attention_fwd_workspace_bytes, nW, heads, device=qkv.device)
         be.check(be.lib.vdk_window_attention_fwd(be.ptr(qkv), C3, be.ptr(o), Cc, be.ptr(lse), be.ptr(biasc), be.ptr(mask), nW, windows, heads, N, Cc // heads, scale,
-                                                 be.ptr(rowidx), be.ptr(ws), ws.numel(), be.stream()), "vdk_window_attention_fwd")
+                                                 be.ptr(rowidx), be.ptr(ws), n, be.stream()), "vdk_window_attention_fwd")
         ctx.save_for_backward(qkv, o, lse, biasc)
         ctx.mask, ctx.heads, ctx.be, ctx.scale, ctx.rowidx = mask, heads, be, scale, rowidx
         return o
@@ -232,62 +151,17 @@ class _WinAttn(torch.autograd.Function):
         T, C3 = qkv.shape
         Cc = C3 // 3
         windows = T // N
-        do = _bf(be, do.contiguous())
+        nW = 0 if mask is None else mask.shape[0]
+        do = _cast(be, do.contiguous(), torch.bfloat16)
         dqkv = torch.empty_like(qkv)
         dbias = torch.empty((heads, N, N), dtype=torch.float32, device=qkv.device)
-        need = C.c_size_t(0)
-        be.check(be.lib.vdk_window_attention_bwd_workspace_bytes(windows, 0 if mask is None else mask.shape[0], heads, C.byref(need)),
-                 "vdk_window_attention_bwd_workspace_bytes")
-        ws = torch.empty(need.value, dtype=torch.uint8, device=qkv.device)
-        be.check(be.lib.vdk_window_attention_bwd(be.ptr(qkv), C3, be.ptr(o), be.ptr(do), Cc, be.ptr(lse), be.ptr(biasc), be.ptr(mask), 0 if mask is None else mask.shape[0],
-                                                 windows, heads, N, Cc // heads, ctx.scale, be.ptr(ctx.rowidx), be.ptr(dqkv), C3, be.ptr(dbias), be.ptr(ws), ws.numel(),
-                                                 be.stream()), "vdk_window_attention_bwd")
+        ws, n = ops._ws(be, be.lib.vdk_window_attention_bwd_workspace_bytes, windows, nW, heads, device=qkv.device)
+        be.check(be.lib.vdk_window_attention_bwd(be.ptr(qkv), C3, be.ptr(o), be.ptr(do), Cc, be.ptr(lse), be.ptr(biasc), be.ptr(mask), nW, windows, heads, N, Cc // heads,
+                                                 ctx.scale, be.ptr(ctx.rowidx), be.ptr(dqkv), C3, be.ptr(dbias), be.ptr(ws), n, be.stream()), "vdk_window_attention_bwd")
         return dqkv, dbias, None, None, None, None
 
 
-class _BiasGather(torch.autograd.Function):
-    """relative_position_bias_table [169, H] -> bias [H, 49, 49] (an index gather); the backward sums each table entry's <= 49 uses in a fixed order with one gather kernel
-    (timm's index backward is an index_add with atomics)"""
-
-    @staticmethod
-    def forward(ctx, table, index, uses, be):
-        ctx.be, ctx.uses, ctx.shape = be, uses, table.shape
-        return table.detach()[index.view(-1)].view(N, N, -1).permute(2, 0, 1).contiguous()
-
-    @staticmethod
-    def backward(ctx, dbias):
-        be, uses = ctx.be, ctx.uses
-        R, H = ctx.shape
-        dbias = dbias.contiguous()
-        dtable = torch.empty((R, H), dtype=torch.float32, device=dbias.device)
-        be.check(be.lib.vdk_relpos_bias_table_grad(be.ptr(dbias), be.ptr(uses), R, uses.shape[1], H, N * N, be.ptr(dtable), be.stream()), "vdk_relpos_bias_table_grad")
-        return dtable, None, None, None
-
-
-class _Pool(torch.autograd.Function):
-    """global average pool over the tokens of f32 NHWC rows"""
-
-    @staticmethod
-    def forward(ctx, x, be):
-        B, H, W, Cc = x.shape
-        out = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
-        be.check(be.lib.vdk_avgpool_rows_f32_fwd(be.ptr(x.contiguous()), be.ptr(out), B, H * W, Cc, be.stream()), "vdk_avgpool_rows_f32_fwd")
-        ctx.be, ctx.shape = be, x.shape
-        return out
-
-    @staticmethod
-    def backward(ctx, dy):
-        B, H, W, Cc = ctx.shape
-        dx = torch.empty(ctx.shape, dtype=torch.float32, device=dy.device)
-        ctx.be.check(ctx.be.lib.vdk_avgpool_rows_f32_bwd(ctx.be.ptr(dy.contiguous()), ctx.be.ptr(dx), None, B, H * W, Cc, ctx.be.stream()), "vdk_avgpool_rows_f32_bwd")
-        return dx, None
-
-
 # ---- modules with timm's names -------------------------------------------------------------------------------------------------------------------
-class _Holder(nn.Module):
-    pass
-
-
 class WindowAttention(nn.Module):
     def __init__(self, dim: int, heads: int, be, dev):
         super().__init__()
@@ -296,12 +170,7 @@ class WindowAttention(nn.Module):
         nn.init.trunc_normal_(self.relative_position_bias_table, std=.02)
         idx = _rel_index(WS)
         self.register_buffer("relative_position_index", idx.to(dev), persistent=False)
-        uses = torch.full(((2 * WS - 1) ** 2, N), -1, dtype=torch.int32)            # for the gather's backward: where each table entry is used (-1 padded)
-        flat = idx.view(-1)
-        for r in range((2 * WS - 1) ** 2):
-            pos = (flat == r).nonzero().view(-1)
-            uses[r, :pos.numel()] = pos.to(torch.int32)
-        self.register_buffer("_uses", uses.to(dev), persistent=False)
+        self.register_buffer("_uses", _uses_table(idx, WS).to(dev), persistent=False)
         self.qkv = nn.Linear(dim, 3 * dim, device=dev)
         self.proj = nn.Linear(dim, dim, device=dev)
 
@@ -329,12 +198,8 @@ class SwinBlock(nn.Module):
         self._perm = {}
 
     def _perms(self, B: int, dev):
-        """the image-order row of every (window, token) of the (cyclically shifted) window partition of a batch of B maps"""
-        if B not in self._perm:
-            idx = torch.arange(B * self.res * self.res).view(B, self.res, self.res, 1)
-            if self.shift:
-                idx = torch.roll(idx, (-self.shift, -self.shift), (1, 2))
-            self._perm = {B: _partition(idx, WS).view(-1).to(torch.int32).to(dev)}
+        if B not in self._perm:      # (one batch size kept)
+            self._perm = {B: _window_rows(self.res, self.shift, WS, B).to(dev)}
         return self._perm[B]
 
     def forward(self, x):                                       # f32 [B, H, W, C]
@@ -346,13 +211,13 @@ class SwinBlock(nn.Module):
         so a gradient reaches its consumer as the very tensor its producer made (with its bf16 copy attached, _LNRes)"""
         Cc = x.shape[1]
         be, a = self.be, self.attn
-        h, xs = _LNRes.apply(x, self.norm1.weight, self.norm1.bias, self.eps, be)                        # xs = x: the shortcut, routed through the norm's node
-        qkv = _Lin.apply(h, a.qkv.weight, a.qkv.bias, None, torch.bfloat16, be)                          # rows stay in image order: the kernels follow the window index
+        h, xs = _LNRes.apply(x, self.norm1.weight, self.norm1.bias, self.eps, BF, be)                       # xs = x: the shortcut, routed through the norm's node
+        qkv = _Lin.apply(h, a.qkv.weight, a.qkv.bias, None, BF, BF, be)                                 # rows stay in image order: the kernels follow the window index
         bias = _BiasGather.apply(a.relative_position_bias_table, a.relative_position_index, a._uses, be)
         o = _WinAttn.apply(qkv, bias, self.attn_mask, self.heads, be, self._perms(B, x.device))
-        y = _Lin.apply(o, a.proj.weight, a.proj.bias, xs, torch.float32, be)                             # shortcut added in the GEMM epilogue
-        h2, ys = _LNRes.apply(y, self.norm2.weight, self.norm2.bias, self.eps, be)
-        return _Mlp.apply(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.fc2.bias, ys, be)
+        y = _Lin.apply(o, a.proj.weight, a.proj.bias, xs, torch.float32, BF, be)                         # shortcut added in the GEMM epilogue
+        h2, ys = _LNRes.apply(y, self.norm2.weight, self.norm2.bias, self.eps, BF, be)
+        return _Mlp.apply(h2, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.fc2.bias, ys, BF, be)
 
 
 class PatchMerging(nn.Module):
@@ -363,10 +228,8 @@ class PatchMerging(nn.Module):
         self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False, device=dev)
 
     def forward(self, x):
-        B, H, W, Cc = x.shape
-        x = x.reshape(B, H // 2, 2, W // 2, 2, Cc).permute(0, 1, 3, 4, 2, 5).flatten(3)
-        h = _LN.apply(x, self.norm.weight, self.norm.bias, self.eps, torch.bfloat16, self.be)
-        return _Lin.apply(h, self.reduction.weight, None, None, torch.float32, self.be)
+        h = _LN.apply(_merge2x2(x), self.norm.weight, self.norm.bias, self.eps, BF, self.be)
+        return _Lin.apply(h, self.reduction.weight, None, None, torch.float32, BF, self.be)
 
 
 class SwinStage(nn.Module):
@@ -419,25 +282,15 @@ class SwinTransformerAutograd(nn.Module):
         self.reset_parameters()
 
     def reset_parameters(self):
-        """the reference's override after timm's init (classify_model.py:70-81): N(0, 0.02) for every Conv2d / Linear weight, zeros for Linear bias"""
-        for m in self.modules():
-            if isinstance(m, nn.Conv2d):
-                nn.init.normal_(m.weight, mean=0, std=0.02)
-            elif isinstance(m, nn.Linear):
-                nn.init.normal_(m.weight, mean=0, std=0.02)
-                if m.bias is not None:
-                    nn.init.zeros_(m.bias)
+        _init_conv_linear(self)
 
     def forward_features(self, x: torch.Tensor) -> torch.Tensor:
         s, be = self.spec, self.be
-        if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (s.in_chans, s.img_size, s.img_size):
-            raise ValueError(f"expected float32 [B, {s.in_chans}, {s.img_size}, {s.img_size}], got {tuple(x.shape)} {x.dtype}")
+        check_image(x, s.in_chans, s.img_size)
         B = x.shape[0]
         g = s.img_size // 4
-        # 4 x 4 / stride 4 convolution = a Linear over (c, ky, kx) patches (the patch operand is an index permutation of the image)
-        pt = x.reshape(B, s.in_chans, g, 4, g, 4).permute(0, 2, 4, 1, 3, 5).reshape(B * g * g, s.in_chans * 16)
         pe = self.patch_embed
-        y = _Lin.apply(pt, pe.proj.weight.view(s.embed_dim, -1), pe.proj.bias, None, torch.float32, be)
+        y = _Lin.apply(_stem_patches(x), pe.proj.weight.view(s.embed_dim, -1), pe.proj.bias, None, torch.float32, BF, be)
         y = _LN.apply(y.view(B, g, g, s.embed_dim), pe.norm.weight, pe.norm.bias, s.ln_eps, torch.float32, be)
         y = self.layers(y)
         return _LN.apply(y, self.norm.weight, self.norm.bias, s.ln_eps, torch.float32, be)
@@ -446,66 +299,41 @@ class SwinTransformerAutograd(nn.Module):
         f = self.forward_features(x)
         if self.num_classes == 0:
             return f
-        from .vit import _LinearFn
         return _LinearFn.apply(_Pool.apply(f, self.be), self.head.fc.weight, self.head.fc.bias, self.be)
 
 
 # =====================================================================================================================================================
 # the native engine
-class SwinEngine:
+class SwinEngine(FlatEngine):
     """owns the flat HBM buffers (fp32 master params, bf16 operand copies, grads, workspace) and calls vdk_swin_forward / vdk_swin_backward; the interface of vit.VitEngine
     (forward -> padded logits, backward(dlogits bf16), refresh_weights, params / grads / wb16 / n_floats / cp), so the fused train steps take either"""
 
     fp8 = 0
 
     def __init__(self, spec: SwinSpec, device=None, backend: Optional[_lib.Backend] = None, operand: str = "bf16"):
-        from . import _abi
-        from .vit import OPERANDS
-        assert operand in OPERANDS, operand
-        # 16-bit format of the GEMM / window-attention operands and the saved activations: "bf16", or "fp16" = what the reference's `torch.autocast(device_type=...)`
+        # operand: 16-bit format of the GEMM / window-attention operands and the saved activations: "bf16", or "fp16" = what the reference's `torch.autocast(device_type=...)`
         # (engine/procedure/train.py:118, no dtype => float16 on a GPU) computes in; vit.FusedTrainStep then runs the GradScaler protocol of train.py:203-215 around the step
-        self.operand = operand
-        self.spec = spec
+        super().__init__(spec, device, backend, operand)
         # Stochastic depth (timm DropPath).  timm builds swin_* with drop_path_rate = 0.1 (block k of n gets rate 0.1 * k / (n - 1)); in training every block's two branches are
         # multiplied per sample by mask / keep_prob before the shortcut is added.  forward(training=True) draws the factors [2 * blocks, B] on the device from torch's generator
         # and hands them to the engine (VdkSwinConfig.drop_path); the backward of that forward reads the same buffer.  0.0: no factors, the epilogues are untouched.
         self.drop_path_rate = 0.0
         self._dp: Optional[torch.Tensor] = None
-        self.be = backend or _lib.load()
-        self.device = torch.device(device if device is not None else ("cuda" if self.be.device_only else "cpu"))
         cfg = self._cfg(1)
         nf, nt, ntr = _abi.I64(0), _abi.I32(0), _abi.I64(0)
         self.be.check(self.be.lib.vdk_swin_param_count(C.byref(cfg), C.byref(nf), C.byref(nt), C.byref(ntr)), "vdk_swin_param_count")
         self.n_floats, self.n_tensors, self.n_transposed = nf.value, nt.value, ntr.value
-        self.entries = []
-        name = C.create_string_buffer(96)
-        off, numel, ndim = _abi.I64(0), _abi.I64(0), _abi.I32(0)
-        shape = (_abi.I64 * 4)()
-        for i in range(self.n_tensors):
-            self.be.check(self.be.lib.vdk_swin_param_info(C.byref(cfg), i, name, 96, C.byref(off), C.byref(numel), shape, C.byref(ndim)), "vdk_swin_param_info")
-            self.entries.append((name.value.decode(), off.value, numel.value, tuple(shape[j] for j in range(ndim.value))))
-        dev = self.device
-        self.params = torch.zeros(self.n_floats, dtype=torch.float32, device=dev)
-        self.grads = torch.zeros(self.n_floats, dtype=torch.float32, device=dev)
-        self.wb16 = torch.zeros(self.n_floats, dtype=self.op_dtype, device=dev)
-        self.wt16 = torch.zeros(self.n_transposed, dtype=self.op_dtype, device=dev)
+        self.entries = self._read_entries(self.be.lib.vdk_swin_param_info, cfg, self.n_tensors)
+        self._alloc(wt16=(self.n_transposed, self.op_dtype))
         self.cp = (spec.num_classes + 7) // 8 * 8
         nst = len(spec.depths)
         self.features = spec.embed_dim * 2 ** (nst - 1)
         self.map_rows = (spec.img_size // 4 // 2 ** (nst - 1)) ** 2      # rows of the final map per image (49 for the 4-stage family at 224)
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_batch = -1
         self._out: Optional[torch.Tensor] = None
-        self._weights_version = None
-
-    @property
-    def op_dtype(self) -> torch.dtype:
-        from .vit import OPERANDS
-        return OPERANDS[self.operand]
+        self._fwd_serial = 0
 
     def set_operand(self, operand: str) -> None:
         """switch between bf16 and fp16 operands (the fp32 master weights stay; the 16-bit copies are rebuilt on the next forward)"""
-        from .vit import OPERANDS
         assert operand in OPERANDS, operand
         if operand == self.operand:
             return
@@ -514,16 +342,7 @@ class SwinEngine:
         self.wt16 = torch.zeros(self.n_transposed, dtype=self.op_dtype, device=self.device)
         self._weights_version = None
 
-    def __deepcopy__(self, memo):
-        import copy
-        new = object.__new__(SwinEngine)
-        memo[id(self)] = new
-        for k, v in self.__dict__.items():
-            setattr(new, k, v if k == "be" else copy.deepcopy(v, memo))
-        return new
-
     def _cfg(self, batch: int, pass_dp: bool = False):
-        from . import _abi
         s = self.spec
         I4 = _abi.I32 * 4
         pad = lambda t: I4(*(tuple(t) + (0,) * (4 - len(t))))      # shallower members of the family (tests): trailing zeros
@@ -550,12 +369,7 @@ class SwinEngine:
 
     def _workspace(self, batch: int) -> torch.Tensor:
         if self._ws is None or self._ws_batch != batch:
-            need = C.c_size_t(0)
-            cfg = self._cfg(batch)
-            self.be.check(self.be.lib.vdk_swin_workspace_bytes(C.byref(cfg), C.byref(need)), "vdk_swin_workspace_bytes")
-            if self._ws is None or self._ws.numel() < need.value:
-                self._ws = None
-                self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            self._grow("_ws", self.be.lib.vdk_swin_workspace_bytes, self._cfg(batch))
             self._ws_batch = batch
             shape = (batch, self.cp) if self.cp else (batch * self.map_rows, self.features)
             self._out = torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -567,32 +381,19 @@ class SwinEngine:
         be.check(be.lib.vdk_swin_refresh_weights(C.byref(cfg), be.ptr(self.params), be.ptr(self.wb16), be.ptr(self.wt16), int(skip_wb16), be.stream()), "vdk_swin_refresh_weights")
         self._weights_version = self.params._version
 
-    def _ensure_fresh(self) -> None:
-        if self._weights_version != self.params._version:
-            self.refresh_weights()
-
     def fp8_update(self) -> None:      # (protocol of the fused train step: this family has no fp8 mode)
         pass
-
-    def view(self, flat: torch.Tensor, name: str) -> torch.Tensor:
-        """the tensor `name` (timm key) inside a flat buffer laid out like params (grads, a momentum or EMA buffer of the fused step)"""
-        for n, off, numel, shape in self.entries:
-            if n == name:
-                return flat[off:off + numel].view(shape)
-        raise KeyError(name)
 
     def forward(self, x: torch.Tensor, training: bool = True, drop_path: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x f32 [B, C, H, W] -> logits f32 [B, Cp] (padded columns beyond num_classes) or, in feature mode, the normed map rows f32 [B * 49, 8 E].
         training: stochastic depth is active (drop_path_rate > 0): factors are drawn per call, or taken from `drop_path` ([2 * blocks, B], tests hand the oracle the same ones)."""
         s = self.spec
-        if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (s.in_chans, s.img_size, s.img_size):
-            raise ValueError(f"expected float32 [B, {s.in_chans}, {s.img_size}, {s.img_size}], got {tuple(x.shape)} {x.dtype}")
-        x = x.contiguous()
+        x = self._image(x)
         B = x.shape[0]
         ws = self._workspace(B)
         self._ensure_fresh()
         self._dp = None
-        self._fwd_serial = getattr(self, "_fwd_serial", 0) + 1      # (the workspace and the factors below belong to THIS forward: _SwinFunction.backward checks it is still the last one)
+        self._fwd_serial += 1      # (the workspace and the factors below belong to THIS forward: _SwinFunction.backward checks it is still the last one)
         if training:
             self._dp = drop_path.to(self.device, torch.float32).contiguous() if drop_path is not None else self.draw_drop_path(B)
             assert self._dp is None or tuple(self._dp.shape) == (2 * sum(s.depths), B)
@@ -605,28 +406,19 @@ class SwinEngine:
         """Evaluation forward with every contraction on the fp32 MFMA (vdk_swin_forward_f32, fused fp32 window attention): logits f32 [B, Cp] / map rows f32 [B * 49, 8 E]
         within ~1e-6 of the reference's PyTorch-CPU fp32 path.  Reads the fp32 master weights, never drops a path, keeps nothing for a backward and has a workspace of its
         own: the training forward's workspace, factors and serial stay as they are, so it may run between a forward and its backward."""
-        s = self.spec
-        if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (s.in_chans, s.img_size, s.img_size):
-            raise ValueError(f"expected float32 [B, {s.in_chans}, {s.img_size}, {s.img_size}], got {tuple(x.shape)} {x.dtype}")
-        x = x.contiguous()
+        x = self._image(x)
         B = x.shape[0]
         cfg = self._cfg(B)
         be = self.be
-        need = C.c_size_t(0)
-        be.check(be.lib.vdk_swin_workspace_f32_bytes(C.byref(cfg), C.byref(need)), "vdk_swin_workspace_f32_bytes")
-        if getattr(self, "_ws32", None) is None or self._ws32.numel() < need.value:
-            self._ws32 = None
-            self._ws32 = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        ws = self._grow("_ws32", be.lib.vdk_swin_workspace_f32_bytes, cfg)
         shape = (B, self.cp) if self.cp else (B * self.map_rows, self.features)
         out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        be.check(be.lib.vdk_swin_forward_f32(C.byref(cfg), be.ptr(x), be.ptr(self.params), be.ptr(self._ws32), self._ws32.numel(), be.ptr(out), be.stream()),
-                 "vdk_swin_forward_f32")
+        be.check(be.lib.vdk_swin_forward_f32(C.byref(cfg), be.ptr(x), be.ptr(self.params), be.ptr(ws), ws.numel(), be.ptr(out), be.stream()), "vdk_swin_forward_f32")
         return out
 
     def backward(self, dout: torch.Tensor, on_ready=None) -> torch.Tensor:
         """dlogits in the operand format [B, Cp] (feature mode: f32 [B * 49, 8 E]) -> self.grads (flat fp32, overwritten); needs the workspace of the matching forward"""
-        from . import _abi
-        B = dout.shape[0] if self.cp else dout.shape[0] // self.map_rows
+        B =dout.shape[0] if self.cp else dout.shape[0] // self.map_rows
         assert B == self._ws_batch and dout.is_contiguous()
         assert (dout.dtype == self.op_dtype and dout.shape[1] == self.cp) if self.cp else (dout.dtype == torch.float32 and dout.shape[1] == self.features)
         cfg = self._cfg(B, pass_dp=True)
@@ -656,29 +448,23 @@ class _SwinFunction(torch.autograd.Function):
     def backward(ctx, dout):
         module = ctx.module
         eng = module.engine
-        be = eng.be
         if eng._fwd_serial != ctx.serial:
             raise RuntimeError("another forward ran through this Swin engine since the one being differentiated: its saved activations and stochastic-depth factors are gone "
                                "(one engine keeps ONE forward's workspace; run backward before the next forward)")
         if eng.cp == 0:
             g = eng.backward(dout.contiguous().view(-1, eng.features))
         else:
-            B, Cn = dout.shape
-            stage = torch.zeros((B, eng.cp), dtype=torch.float32, device=dout.device)
-            stage[:, :Cn].copy_(dout)
-            dl = torch.empty((B, eng.cp), dtype=eng.op_dtype, device=dout.device)
-            cast = be.lib.vdk_cast_f32_f16 if eng.operand == "fp16" else be.lib.vdk_cast_f32_bf16
-            be.check(cast(be.ptr(stage), be.ptr(dl), stage.numel(), be.stream()), "vdk_cast_f32_16")
-            g = eng.backward(dl)
-        grads = tuple(g[off:off + numel].view(shape) for (_, off, numel, shape) in eng.entries)
-        return (None, None) + grads
+            g = eng.backward(pad_cast_dlogits(eng, dout))
+        return module._flat_grads(g)
 
 
-class SwinTransformer(nn.Module):
+class SwinTransformer(FlatParamModule):
     """Drop-in for the object `timm.create_model('swin_*_patch4_window7_224', pretrained=False, num_classes=C)` hands the reference, on the native engine.  The module tree
     mirrors timm's (patch_embed.proj / norm, layers.i.downsample.{norm, reduction}, layers.i.blocks.j.{norm1, attn.{relative_position_bias_table, qkv, proj}, norm2,
     mlp.{fc1, fc2}}, norm, head.fc) with parameter-only holders, so named_parameters() / state_dict() / load_state_dict() carry timm's key names; every Parameter is a view
     into the engine's flat fp32 buffer.  forward(x [B, 3, 224, 224]) -> logits [B, C]; num_classes = 0: the normed NHWC map [B, 7, 7, C_last] (timm's forward_features)."""
+
+    family = "Swin"
 
     def __init__(self, spec: SwinSpec, device=None, backend: Optional[_lib.Backend] = None, seed: Optional[int] = None, operand: str = "bf16", drop_path_rate: float = 0.0):
         super().__init__()
@@ -690,24 +476,13 @@ class SwinTransformer(nn.Module):
         self.be = self.engine.be
         self.num_classes = spec.num_classes
         self.num_features = self.engine.features
-        self._plist = []
-        for name, off, numel, shape in self.engine.entries:
-            p = nn.Parameter(self.engine.params[off:off + numel].view(shape))
-            parts = name.split(".")
-            m = self
-            for part in parts[:-1]:
-                if part not in m._modules:
-                    m.add_module(part, _Holder())
-                m = m._modules[part]
-            m.register_parameter(parts[-1], p)
-            self._plist.append((name, p))
+        self._build_tree()
         self.reset_parameters(seed)
 
     def reset_parameters(self, seed: Optional[int] = None) -> None:
         """timm's defaults + the reference's override after them (classify_model.py:70-81): N(0, 0.02) for every Conv2d / Linear weight, zeros for Linear bias (the
         convolution's bias keeps its default), LayerNorm (1, 0), relative_position_bias_table trunc_normal(0.02)"""
-        gen = torch.Generator(device="cpu")
-        gen.manual_seed(seed if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
+        gen = seeded_generator(seed)
         s = self.spec
         with torch.no_grad():
             for name, p in self._plist:
@@ -723,32 +498,6 @@ class SwinTransformer(nn.Module):
                 else:
                     v = torch.empty(p.shape).normal_(0, 0.02, generator=gen)
                 p.copy_(v.to(p.device))
-
-    def _sync_flat(self) -> None:
-        eng = self.engine
-        base = eng.params.data_ptr()
-        for (name, off, numel, shape), (_, p) in zip(eng.entries, self._plist):
-            if p.data_ptr() != base + off * 4:
-                with torch.no_grad():
-                    eng.params[off:off + numel].view(shape).copy_(p.detach().to(eng.device))
-                    p.data = eng.params[off:off + numel].view(shape)
-
-    def _apply(self, fn, recurse=True):
-        probe = fn(torch.zeros(1, dtype=torch.float32, device=self.engine.device))
-        if probe.device != self.engine.device or probe.dtype != torch.float32:
-            if probe.dtype != torch.float32:
-                raise RuntimeError("visiondk_amd Swin keeps fp32 master weights; bf16 copies are internal")
-            if self.engine.be.device_only and probe.device.type != "cuda":
-                raise RuntimeError("visiondk_amd Swin lives on the GPU (no CPU fallback)")
-            eng = self.engine
-            eng.device = probe.device
-            for attr in ("params", "grads", "wb16", "wt16"):
-                setattr(eng, attr, getattr(eng, attr).to(probe.device))
-            eng._ws, eng._ws_batch, eng._weights_version = None, -1, None
-            eng._ws32 = None
-            for (name, off, numel, shape), (_, p) in zip(eng.entries, self._plist):
-                p.data = eng.params[off:off + numel].view(shape)
-        return self
 
     def forward_features(self, x: torch.Tensor) -> torch.Tensor:
         if self.num_classes != 0:

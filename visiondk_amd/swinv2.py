@@ -25,7 +25,6 @@ The batch-independent parameter side stays in fp32 torch ops on the device: the 
 vdk_relpos_bias_table_grad (fixed order).  The two residual adds per block and the widening of a 16-bit GEMM output for the fp32 LayerNorm are torch ops."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -34,13 +33,13 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from ._abi import ACT_DGELU, ACT_GELU
-from .swin import _Holder, _LN, _Pool, _partition, _shift_mask, _wgrad
+from ._engine import OPERANDS, _Holder, check_image
+from ._nodes import _BiasGather, _cast, _LinearFn, _Lin, _LN, _Mlp, _Pool
+from .swin import _init_conv_linear, _merge2x2, _rel_index, _shift_mask, _stem_patches, _uses_table, _window_rows
 
 WS = 8
 N = WS * WS
 LOGIT_MAX = math.log(100.0)       # timm clamps logit_scale at ln(1 / 0.01)
-_DT = {"bf16": torch.bfloat16, "fp16": torch.float16}
 _OPF = {torch.bfloat16: 0, torch.float16: 1}
 
 
@@ -82,80 +81,10 @@ def coords_table(ws: int = WS) -> torch.Tensor:
 
 
 def rel_index(ws: int = WS) -> torch.Tensor:
-    coords = torch.stack(torch.meshgrid(torch.arange(ws), torch.arange(ws), indexing="ij")).flatten(1)
-    rel = (coords[:, :, None] - coords[:, None, :]).permute(1, 2, 0).contiguous()
-    rel[:, :, 0] += ws - 1
-    rel[:, :, 1] += ws - 1
-    rel[:, :, 0] *= 2 * ws - 1
-    return rel.sum(-1)
+    return _rel_index(ws)
 
 
-# ---- autograd nodes over the kernels, in the operand format dt -------------------------------------------------------------------------------------
-def _cast(be, t: torch.Tensor, dt) -> torch.Tensor:
-    return t if t.dtype == dt else ops.cast_16(t.contiguous(), dt, backend=be)
-
-
-def _wt(be, w: torch.Tensor, dt) -> torch.Tensor:
-    """w f32 [out, in] -> dt [in, out]: the B operand of dX = dY W (out a multiple of 8 everywhere in this model)"""
-    if dt == torch.bfloat16:
-        return ops.transpose_cast(w.detach().contiguous(), backend=be)
-    return ops.transpose_pad(ops.cast_16(w.detach().contiguous(), dt, backend=be), rpad=w.shape[0], backend=be)
-
-
-def _colsum(be, dyb: torch.Tensor) -> torch.Tensor:
-    """f32 column sums of a 16-bit [T, N] gradient (a Linear's bias gradient).  fp16: dY^T 1 on the MFMA GEMM, an fp32 sum of the stored values like vdk_colsum_bf16's"""
-    if dyb.dtype == torch.bfloat16:
-        return ops.colsum_bf16(dyb, backend=be)
-    ones = torch.ones((dyb.shape[0], 8), dtype=dyb.dtype, device=dyb.device)
-    return _wgrad(be, dyb, ones)[:, 0].contiguous()
-
-
-class _Lin(torch.autograd.Function):
-    """y = x W^T (+ b): 16-bit operands on the MFMA GEMM; y in the operand format (or f32)"""
-
-    @staticmethod
-    def forward(ctx, x, w, b, out_dtype, dt, be):
-        xb = _cast(be, x.contiguous().view(-1, x.shape[-1]), dt)
-        wb = ops.cast_16(w.detach().contiguous(), dt, backend=be)
-        y = ops.gemm_nt(xb, wb, out_dtype=out_dtype, bias=b.detach().contiguous() if b is not None else None, backend=be)
-        ctx.save_for_backward(xb, w)
-        ctx.be, ctx.has_b, ctx.xshape, ctx.xdtype, ctx.dt = be, b is not None, x.shape, x.dtype, dt
-        return y.view(*x.shape[:-1], w.shape[0])
-
-    @staticmethod
-    def backward(ctx, dy):
-        xb, w = ctx.saved_tensors
-        be, dt = ctx.be, ctx.dt
-        dyb = _cast(be, dy.contiguous().view(-1, w.shape[0]), dt)
-        dx = ops.gemm_nt(dyb, _wt(be, w, dt), out_dtype=dt if ctx.xdtype == dt else torch.float32, backend=be)
-        return dx.view(ctx.xshape), _wgrad(be, dyb, xb), _colsum(be, dyb) if ctx.has_b else None, None, None, None
-
-
-class _Mlp(torch.autograd.Function):
-    """fc2(gelu(fc1(x))) in the operand format: fc1 with the GELU epilogue (pre-activation kept), backward with the dGELU epilogue on the fc2 input-gradient GEMM"""
-
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, dt, be):
-        xb = _cast(be, x.contiguous().view(-1, x.shape[-1]), dt)
-        w1b, w2b = ops.cast_16(w1.detach().contiguous(), dt, backend=be), ops.cast_16(w2.detach().contiguous(), dt, backend=be)
-        u = torch.empty((xb.shape[0], w1.shape[0]), dtype=dt, device=x.device)
-        g = ops.gemm_nt(xb, w1b, bias=b1.detach(), act=ACT_GELU, aux=u, backend=be)
-        y = ops.gemm_nt(g, w2b, bias=b2.detach(), backend=be)
-        ctx.save_for_backward(xb, u, g, w1, w2)
-        ctx.be, ctx.shape, ctx.dt = be, x.shape, dt
-        return y.view(x.shape)
-
-    @staticmethod
-    def backward(ctx, dy):
-        xb, u, g, w1, w2 = ctx.saved_tensors
-        be, dt = ctx.be, ctx.dt
-        dyb = _cast(be, dy.contiguous().view(-1, w2.shape[0]), dt)
-        du = ops.gemm_nt(dyb, _wt(be, w2, dt), act=ACT_DGELU, aux=u, backend=be)
-        dw2, db2 = _wgrad(be, dyb, g), _colsum(be, dyb)
-        dx = ops.gemm_nt(du, _wt(be, w1, dt), out_dtype=torch.float32, backend=be)
-        return dx.view(ctx.shape), _wgrad(be, du, xb), _colsum(be, du), dw2, db2, None, None
-
-
+# ---- the attention node (the model-independent nodes: _nodes.py) -----------------------------------------------------------------------------------
 class _CosAttn(torch.autograd.Function):
     """the attention step of timm's SwinV2 WindowAttention on 16-bit qkv rows (csrc/window_attention_cos.hip); rowidx (int32 [T], a permutation) = the tensor row of every
     (window, token): qkv and o stay in image order.  logit_scale f32 [H]: tau = exp(clamp) goes to the kernel, d(tau) comes back through logit_scale_grad."""
@@ -194,24 +123,6 @@ class _CosAttn(torch.autograd.Function):
         return dqkv, logit_scale_grad(dtau, logit_scale), dbias, None, None, None, None
 
 
-class _BiasGather(torch.autograd.Function):
-    """cpb_mlp(table) [225, H] -> [H, 64, 64] (an index gather); the backward sums each entry's <= 64 uses in a fixed order with one gather kernel"""
-
-    @staticmethod
-    def forward(ctx, table, index, uses, be):
-        ctx.be, ctx.uses, ctx.shape = be, uses, table.shape
-        return table.detach()[index.view(-1)].view(N, N, -1).permute(2, 0, 1).contiguous()
-
-    @staticmethod
-    def backward(ctx, dbias):
-        be, uses = ctx.be, ctx.uses
-        R, H = ctx.shape
-        dbias = dbias.contiguous()
-        dtable = torch.empty((R, H), dtype=torch.float32, device=dbias.device)
-        be.check(be.lib.vdk_relpos_bias_table_grad(be.ptr(dbias), be.ptr(uses), R, uses.shape[1], H, N * N, be.ptr(dtable), be.stream()), "vdk_relpos_bias_table_grad")
-        return dtable, None, None, None
-
-
 # ---- modules with timm's names -------------------------------------------------------------------------------------------------------------------
 class WindowAttention(nn.Module):
     def __init__(self, dim: int, heads: int, dev):
@@ -222,13 +133,7 @@ class WindowAttention(nn.Module):
         self.register_buffer("relative_coords_table", coords_table().to(dev), persistent=False)
         idx = rel_index()
         self.register_buffer("relative_position_index", idx.to(dev), persistent=False)
-        R = (2 * WS - 1) ** 2
-        uses = torch.full((R, N), -1, dtype=torch.int32)                                # for the gather's backward: where each table entry is used (-1 padded)
-        flat = idx.view(-1)
-        for r in range(R):
-            pos = (flat == r).nonzero().view(-1)
-            uses[r, :pos.numel()] = pos.to(torch.int32)
-        self.register_buffer("_uses", uses.to(dev), persistent=False)
+        self.register_buffer("_uses", _uses_table(idx, WS).to(dev), persistent=False)
         self.qkv = nn.Linear(dim, 3 * dim, bias=False, device=dev)
         self.q_bias = nn.Parameter(torch.zeros(dim, device=dev))
         self.register_buffer("k_bias", torch.zeros(dim, device=dev), persistent=False)
@@ -264,12 +169,8 @@ class SwinV2Block(nn.Module):
         self._perm = {}
 
     def _perms(self, B: int, dev):
-        """the image-order row of every (window, token) of the (cyclically shifted) window partition of a batch of B maps"""
-        if B not in self._perm:
-            idx = torch.arange(B * self.res * self.res).view(B, self.res, self.res, 1)
-            if self.shift:
-                idx = torch.roll(idx, (-self.shift, -self.shift), (1, 2))
-            self._perm = {B: _partition(idx, WS).view(-1).to(torch.int32).to(dev)}
+        if B not in self._perm:      # (one batch size kept)
+            self._perm = {B: _window_rows(self.res, self.shift, WS, B).to(dev)}
         return self._perm[B]
 
     def rows(self, x, B: int, f1=None, f2=None):
@@ -278,12 +179,12 @@ class SwinV2Block(nn.Module):
         tests/test_swinv2.py: with fp32 GEMM outputs feeding the post-norms the fp16 logit_scale gradients sat 3.6 - 4.5 x the 16-bit restatement's own deviation from fp32,
         with the rounding in place every gradient is within 1.7 x."""
         be, a, dt = self.be, self.attn, self.dt
-        qkv = _Lin.apply(x, a.qkv.weight, torch.cat((a.q_bias, a.k_bias, a.v_bias)), dt, dt, be)
+        qkv = _Lin.apply(x, a.qkv.weight, torch.cat((a.q_bias, a.k_bias, a.v_bias)), None, dt, dt, be)
         o = _CosAttn.apply(qkv, a.logit_scale.view(-1), a.bias(be), self.attn_mask, self.heads, be, self._perms(B, x.device))
-        h = _LN.apply(_Lin.apply(o, a.proj.weight, a.proj.bias, dt, dt, be).float(), self.norm1.weight, self.norm1.bias, self.eps, torch.float32, be)
+        h = _LN.apply(_Lin.apply(o, a.proj.weight, a.proj.bias, None, dt, dt, be).float(), self.norm1.weight, self.norm1.bias, self.eps, torch.float32, be)
         x = x + (h if f1 is None else h * f1)
         m = self.mlp
-        h = _LN.apply(_Mlp.apply(x, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, dt, be).float(), self.norm2.weight, self.norm2.bias, self.eps, torch.float32, be)
+        h = _LN.apply(_Mlp.apply(x, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, None, dt, be).float(), self.norm2.weight, self.norm2.bias, self.eps, torch.float32, be)
         return x + (h if f2 is None else h * f2)
 
 
@@ -295,9 +196,7 @@ class PatchMerging(nn.Module):
         self.norm = nn.LayerNorm(2 * dim, eps=eps, device=dev)
 
     def forward(self, x):
-        B, H, W, Cc = x.shape
-        x = x.reshape(B, H // 2, 2, W // 2, 2, Cc).permute(0, 1, 3, 4, 2, 5).flatten(3)
-        y = _Lin.apply(x, self.reduction.weight, None, self.dt, self.dt, self.be).float()
+        y = _Lin.apply(_merge2x2(x), self.reduction.weight, None, None, self.dt, self.dt, self.be).float()
         return _LN.apply(y, self.norm.weight, self.norm.bias, self.eps, torch.float32, self.be)
 
 
@@ -315,11 +214,11 @@ class SwinTransformerV2(nn.Module):
 
     def __init__(self, spec: SwinV2Spec, device=None, backend: Optional[_lib.Backend] = None, seed: Optional[int] = None, operand: str = "bf16", drop_path_rate: float = 0.0):
         super().__init__()
-        if operand not in _DT:
+        if operand not in OPERANDS:
             raise ValueError(f"operand must be 'bf16' or 'fp16', got {operand!r}")
         self.spec, self.operand, self.drop_path_rate = spec, operand, float(drop_path_rate)
         self.be = backend or _lib.load()
-        dt = self.dt = _DT[operand]
+        dt = self.dt = OPERANDS[operand]
         dev = device if device is not None else ("cuda" if self.be.device_only else "cpu")
         if seed is not None:
             torch.manual_seed(seed)
@@ -352,13 +251,7 @@ class SwinTransformerV2(nn.Module):
                 for nrm in (blk.norm1, blk.norm2):
                     nn.init.zeros_(nrm.weight)
                     nn.init.zeros_(nrm.bias)
-        for m in self.modules():
-            if isinstance(m, nn.Conv2d):
-                nn.init.normal_(m.weight, mean=0, std=0.02)
-            elif isinstance(m, nn.Linear):
-                nn.init.normal_(m.weight, mean=0, std=0.02)
-                if m.bias is not None:
-                    nn.init.zeros_(m.bias)
+        _init_conv_linear(self)
 
     def draw_drop_path(self, batch: int) -> Optional[torch.Tensor]:
         """factors f32 [2 * blocks, batch] = Bernoulli(keep) / keep per (branch, sample), as timm's drop_path(); block j's rate is linspace(0, drop_path_rate, blocks)[j],
@@ -371,8 +264,7 @@ class SwinTransformerV2(nn.Module):
 
     def forward_features(self, x: torch.Tensor, drop_path: Optional[torch.Tensor] = None) -> torch.Tensor:
         s, be, dt = self.spec, self.be, self.dt
-        if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (s.in_chans, s.img_size, s.img_size):
-            raise ValueError(f"expected float32 [B, {s.in_chans}, {s.img_size}, {s.img_size}], got {tuple(x.shape)} {x.dtype}")
+        check_image(x, s.in_chans, s.img_size)
         B = x.shape[0]
         if self.training:
             if drop_path is None:
@@ -382,10 +274,8 @@ class SwinTransformerV2(nn.Module):
         if drop_path is not None and tuple(drop_path.shape) != (2 * sum(s.depths), B):
             raise ValueError(f"drop_path must be [{2 * sum(s.depths)}, {B}]")
         g = s.img_size // 4
-        # 4 x 4 / stride 4 convolution = a Linear over (c, ky, kx) patches (the patch operand is an index permutation of the image)
-        pt = x.reshape(B, s.in_chans, g, 4, g, 4).permute(0, 2, 4, 1, 3, 5).reshape(B * g * g, s.in_chans * 16)
         pe = self.patch_embed
-        y = _Lin.apply(pt, pe.proj.weight.view(s.embed_dim, -1), pe.proj.bias, dt, dt, be).float()
+        y = _Lin.apply(_stem_patches(x), pe.proj.weight.view(s.embed_dim, -1), pe.proj.bias, None, dt, dt, be).float()
         y = _LN.apply(y.view(B, g, g, s.embed_dim), pe.norm.weight, pe.norm.bias, s.ln_eps, torch.float32, be)
         k = 0
         for stage in self.layers:
@@ -405,7 +295,6 @@ class SwinTransformerV2(nn.Module):
         f = self.forward_features(x, drop_path)
         if self.num_classes == 0:
             return f
-        from .vit import _LinearFn
         return _LinearFn.apply(_Pool.apply(f, self.be), self.head.fc.weight, self.head.fc.bias, self.be)
 
 

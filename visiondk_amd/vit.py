@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import dataclasses
 import math
+import os
 from dataclasses import dataclass
 from typing import Callable, Optional
 
@@ -22,6 +23,8 @@ import torch
 import torch.nn as nn
 
 from . import _abi, _lib, ops
+from ._engine import OPERANDS, FlatEngine, FlatParamModule, _Holder, pad_cast_dlogits, seeded_generator
+from ._nodes import _LinearFn, _pad4, _wgrad_f32      # noqa: F401  (_pad4 stays importable from here with the other two)
 
 
 @dataclass(frozen=True)
@@ -77,18 +80,11 @@ def spec_from_timm_name(name: str, num_classes: int, img_size: Optional[int] = N
     return VitSpec(num_classes=num_classes, **kw)
 
 
-OPERANDS = {"bf16": torch.bfloat16, "fp16": torch.float16}
-
-
-class VitEngine:
+class VitEngine(FlatEngine):
     def __init__(self, spec: VitSpec, device=None, backend: Optional[_lib.Backend] = None, operand: str = "bf16"):
-        self.spec = spec
-        self.be = backend or _lib.load()
-        self.device = torch.device(device if device is not None else ("cuda" if self.be.device_only else "cpu"))
-        # 16-bit format of the GEMM operands / saved activations / gradient tensors: "bf16" (BASELINE.json configs[1]) or "fp16" -- what the reference's
+        # operand: 16-bit format of the GEMM operands / saved activations / gradient tensors: "bf16" (BASELINE.json configs[1]) or "fp16" -- what the reference's
         # `torch.autocast(device_type=...)` (engine/procedure/train.py:118, no dtype => float16 on a GPU) computes in; see set_operand()
-        assert operand in OPERANDS, operand
-        self.operand = operand
+        super().__init__(spec, device, backend, operand)
         self.fp8 = 0                     # 0 = 16-bit operands; see enable_fp8
         self.fp8_w: Optional[torch.Tensor] = None
         self.fp8_state: Optional[torch.Tensor] = None
@@ -96,48 +92,27 @@ class VitEngine:
         nf, nt, ntr = _abi.I64(0), _abi.I32(0), _abi.I64(0)
         self.be.check(self.be.lib.vdk_vit_param_count(C.byref(cfg), C.byref(nf), C.byref(nt), C.byref(ntr)), "vdk_vit_param_count")
         self.n_floats, self.n_tensors, self.n_transposed = nf.value, nt.value, ntr.value
-        self.entries = []
-        name = C.create_string_buffer(96)
-        off, numel, ndim = _abi.I64(0), _abi.I64(0), _abi.I32(0)
-        shape = (_abi.I64 * 4)()
-        for i in range(self.n_tensors):
-            self.be.check(self.be.lib.vdk_vit_param_info(C.byref(cfg), i, name, 96, C.byref(off), C.byref(numel), shape, C.byref(ndim)),
-                          "vdk_vit_param_info")
-            self.entries.append((name.value.decode(), off.value, numel.value, tuple(shape[j] for j in range(ndim.value))))
-        dev = self.device
-        self.params = torch.zeros(self.n_floats, dtype=torch.float32, device=dev)
-        self.grads = torch.zeros(self.n_floats, dtype=torch.float32, device=dev)
-        self.wb16 = torch.zeros(self.n_floats, dtype=self.op_dtype, device=dev)
-        self.wt16 = torch.zeros(self.n_transposed, dtype=self.op_dtype, device=dev)
+        self.entries = self._read_entries(self.be.lib.vdk_vit_param_info, cfg, self.n_tensors)
+        self._alloc(wt16=(self.n_transposed, self.op_dtype))
         self.cp = (spec.num_classes + 7) // 8 * 8          # 0 in feature mode (num_classes == 0)
         self.tokens = (spec.img_size // spec.patch_size) ** 2 + (1 if spec.class_token else 0)
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_batch = -1
         self._logits: Optional[torch.Tensor] = None
-        self._weights_version = None
         # optional side stream for the weight-gradient GEMMs of vdk_vit_backward.  Measured on MI355X (ViT-B/16 bs256): no gain
         # (49.4 ms/step either way; one 128-KB-LDS workgroup per CU means the two kernels only time-share CUs), so it is off
         # unless VDK_SIDE_STREAM=1.
-        import os
         self.side_stream = (torch.cuda.Stream(device=self.device)
                             if (os.environ.get("VDK_SIDE_STREAM") == "1" and self.be.device_only and self.device.type == "cuda") else None)
 
-    def __deepcopy__(self, memo):   # ModelEMA deep-copies the model; streams and library handles are not copyable
-        import copy
-        new = object.__new__(VitEngine)
-        memo[id(self)] = new
-        for k, v in self.__dict__.items():
-            if k == "side_stream":
-                new.side_stream = torch.cuda.Stream(device=self.device) if v is not None else None
-            else:
-                setattr(new, k, copy.deepcopy(v, memo))
+    def __deepcopy__(self, memo):   # streams are not copyable: the copy gets one of its own
+        side, self.side_stream = self.side_stream, None
+        try:
+            new = super().__deepcopy__(memo)
+        finally:
+            self.side_stream = side
+        new.side_stream = torch.cuda.Stream(device=self.device) if side is not None else None
         return new
 
     # ---- plumbing ------------------------------------------------------------------------------
-    @property
-    def op_dtype(self) -> torch.dtype:
-        return OPERANDS[self.operand]
-
     def set_operand(self, operand: str) -> None:
         """switch the engine between bf16 and fp16 operands (weights stay the fp32 master copy; the 16-bit copies are rebuilt on the next forward)"""
         assert operand in OPERANDS, operand
@@ -156,20 +131,9 @@ class VitEngine:
                               self.fp8, self.be.ptr(self.fp8_w) if self.fp8 else None, self.be.ptr(self.fp8_state) if self.fp8 else None,
                               _abi.F16_ if self.operand == "fp16" else _abi.BF16, 1 if s.pre_norm else 0)
 
-    def view(self, flat: torch.Tensor, name: str) -> torch.Tensor:
-        for n, off, numel, shape in self.entries:
-            if n == name:
-                return flat[off:off + numel].view(shape)
-        raise KeyError(name)
-
     def _workspace(self, batch: int) -> torch.Tensor:
         if self._ws is None or self._ws_batch != batch:
-            need = C.c_size_t(0)
-            cfg = self._cfg(batch)
-            self.be.check(self.be.lib.vdk_vit_workspace_bytes(C.byref(cfg), C.byref(need)), "vdk_vit_workspace_bytes")
-            if self._ws is None or self._ws.numel() < need.value:      # grow-only: OHEM hands the step a different (smaller) batch every iteration
-                self._ws = None
-                self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            self._grow("_ws", self.be.lib.vdk_vit_workspace_bytes, self._cfg(batch))
             self._ws_batch = batch
             shape = (batch, self.cp) if self.cp else (batch * self.tokens, self.spec.dim)   # logits | final-normed tokens
             self._logits = torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -206,17 +170,10 @@ class VitEngine:
             cfg = self._cfg(1)
             self.be.check(self.be.lib.vdk_vit_fp8_update(C.byref(cfg), self.be.stream()), "vdk_vit_fp8_update")
 
-    def _ensure_fresh(self) -> None:
-        if self._weights_version != self.params._version:
-            self.refresh_weights()
-
     # ---- the two calls -----------------------------------------------------------------------------
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x f32 [B, C, H, W] -> logits f32 [B, Cp] (padded columns beyond num_classes); activations stay in the workspace."""
-        s = self.spec
-        if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (s.in_chans, s.img_size, s.img_size):
-            raise ValueError(f"expected float32 [B, {s.in_chans}, {s.img_size}, {s.img_size}], got {tuple(x.shape)} {x.dtype}")
-        x = x.contiguous()
+        x = self._image(x)
         B = x.shape[0]
         ws = self._workspace(B)
         self._ensure_fresh()
@@ -229,21 +186,14 @@ class VitEngine:
     def forward_precise(self, x: torch.Tensor) -> torch.Tensor:
         """Evaluation forward with every contraction on the fp32 MFMA (vdk_vit_forward_f32): logits f32 [B, Cp] / tokens f32 [B*N, D] within
         ~1e-6 of the reference's PyTorch-CPU fp32 path.  Reads the fp32 master weights; keeps nothing for a backward."""
-        s = self.spec
-        if x.dtype != torch.float32 or x.dim() != 4 or tuple(x.shape[1:]) != (s.in_chans, s.img_size, s.img_size):
-            raise ValueError(f"expected float32 [B, {s.in_chans}, {s.img_size}, {s.img_size}], got {tuple(x.shape)} {x.dtype}")
-        x = x.contiguous()
+        x = self._image(x)
         B = x.shape[0]
         cfg = self._cfg(B)
         be = self.be
-        need = C.c_size_t(0)
-        be.check(be.lib.vdk_vit_workspace_f32_bytes(C.byref(cfg), C.byref(need)), "vdk_vit_workspace_f32_bytes")
-        if getattr(self, "_ws32", None) is None or self._ws32.numel() < need.value:
-            self._ws32 = torch.empty(need.value, dtype=torch.uint8, device=self.device)
-        shape = (B, self.cp) if self.cp else (B * self.tokens, s.dim)
+        ws = self._grow("_ws32", be.lib.vdk_vit_workspace_f32_bytes, cfg)
+        shape = (B, self.cp) if self.cp else (B * self.tokens, self.spec.dim)
         out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        be.check(be.lib.vdk_vit_forward_f32(C.byref(cfg), be.ptr(x), be.ptr(self.params), be.ptr(self._ws32), self._ws32.numel(), be.ptr(out), be.stream()),
-                 "vdk_vit_forward_f32")
+        be.check(be.lib.vdk_vit_forward_f32(C.byref(cfg), be.ptr(x), be.ptr(self.params), be.ptr(ws), ws.numel(), be.ptr(out), be.stream()), "vdk_vit_forward_f32")
         return out
 
     def backward(self, dlogits_bf16: torch.Tensor, on_ready: Optional[Callable[[int, int], None]] = None) -> torch.Tensor:
@@ -284,64 +234,32 @@ class _VitFunction(torch.autograd.Function):
     def backward(ctx, dlogits):
         module = ctx.module
         eng = module.engine
-        be = eng.be
         if eng.cp == 0:
-            g = eng.backward(dlogits.contiguous().view(-1, eng.spec.dim))
-            grads = tuple(g[off:off + numel].view(shape) for (_, off, numel, shape) in eng.entries)
-            return (None, None) + grads
-        B, Cn = dlogits.shape
-        # bf16 + zero-padded columns for the head GEMMs: one cast kernel on a padded staging buffer
-        stage = torch.zeros((B, eng.cp), dtype=torch.float32, device=dlogits.device)
-        stage[:, :Cn].copy_(dlogits)
-        # (fp16 operands: under the reference's GradScaler the incoming gradient already carries the loss scale, train.py:205)
-        dl = torch.empty((B, eng.cp), dtype=eng.op_dtype, device=dlogits.device)
-        cast = be.lib.vdk_cast_f32_f16 if eng.operand == "fp16" else be.lib.vdk_cast_f32_bf16
-        be.check(cast(be.ptr(stage), be.ptr(dl), stage.numel(), be.stream()), "vdk_cast_f32_bf16")
-        g = eng.backward(dl)
-        grads = tuple(g[off:off + numel].view(shape) for (_, off, numel, shape) in eng.entries)
-        return (None, None) + grads
+            return module._flat_grads(eng.backward(dlogits.contiguous().view(-1, eng.spec.dim)))
+        return module._flat_grads(eng.backward(pad_cast_dlogits(eng, dlogits)))
 
 
-class _Holder(nn.Module):
-    """empty container mirroring one level of timm's module tree (patch_embed, blocks.3.attn, ...); owns Parameters only"""
-
-
-class VisionTransformer(nn.Module):
+class VisionTransformer(FlatParamModule):
     """Drop-in for the object `timm.create_model('vit_*', pretrained=False, num_classes=C)` hands the reference.
 
     The module tree mirrors timm's (patch_embed.proj, blocks.i.{norm1,attn.qkv,attn.proj,norm2,mlp.fc1,mlp.fc2}, norm, head) with
     parameter-only holder modules, so named_parameters()/state_dict()/load_state_dict() carry timm's key names at any nesting
     depth; every Parameter is a view into the engine's flat fp32 buffer."""
 
+    family = "ViT"
+
     def __init__(self, spec: VitSpec, device=None, backend: Optional[_lib.Backend] = None, seed: Optional[int] = None, operand: str = "bf16"):
         super().__init__()
         self.spec = spec
         self.engine = VitEngine(spec, device=device, backend=backend, operand=operand)
         self.num_classes = spec.num_classes
-        self._plist = []
-        for name, off, numel, shape in self.engine.entries:
-            p = nn.Parameter(self.engine.params[off:off + numel].view(shape))
-            parts = name.split(".")
-            m = self
-            for part in parts[:-1]:
-                if part not in m._modules:
-                    m.add_module(part, _Holder())
-                m = m._modules[part]
-            m.register_parameter(parts[-1], p)
-            self._plist.append((name, p))
+        self._build_tree()
         self.reset_parameters(seed)
-
-    @property
-    def _names(self):   # (timm name, Parameter) pairs in flat-buffer order
-        return self._plist
 
     def reset_parameters(self, seed: Optional[int] = None) -> None:
         """timm defaults + the reference's override (classify_model.py:70-81): N(0,.02) Conv/Linear weights, zero Linear
         biases (conv bias left at its default init), LayerNorm (1,0), pos_embed trunc-normal .02, cls_token normal 1e-6."""
-        gen = torch.Generator(device="cpu")
-        # no explicit seed: draw it from torch's global generator, so that `torch.manual_seed(s)` reproduces the initialisation like it does for the
-        # reference's model (and data-parallel ranks seeded alike start alike even before the broadcast)
-        gen.manual_seed(seed if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item()))
+        gen = seeded_generator(seed)
         s = self.spec
         with torch.no_grad():
             for name, p in self._plist:
@@ -359,32 +277,6 @@ class VisionTransformer(nn.Module):
                 else:
                     v = torch.empty(p.shape).normal_(0, 0.02, generator=gen)
                 p.copy_(v.to(p.device))
-
-    # keep the flat buffer authoritative even if someone re-pointed a parameter (.to(), deepcopy, p.data = ...)
-    def _sync_flat(self) -> None:
-        eng = self.engine
-        base = eng.params.data_ptr()
-        for (name, off, numel, shape), (_, p) in zip(eng.entries, self._plist):
-            if p.data_ptr() != base + off * 4:
-                with torch.no_grad():
-                    eng.params[off:off + numel].view(shape).copy_(p.detach().to(eng.device))
-                    p.data = eng.params[off:off + numel].view(shape)
-
-    def _apply(self, fn, recurse=True):
-        probe = fn(torch.zeros(1, dtype=torch.float32, device=self.engine.device))
-        if probe.device != self.engine.device or probe.dtype != torch.float32:
-            if probe.dtype != torch.float32:
-                raise RuntimeError("visiondk_amd ViT keeps fp32 master weights; bf16 copies are internal")
-            if self.engine.be.device_only and probe.device.type != "cuda":
-                raise RuntimeError("visiondk_amd ViT lives on the GPU (no CPU fallback)")
-            eng = self.engine
-            eng.device = probe.device
-            for attr in ("params", "grads", "wb16", "wt16"):      # (.to keeps each buffer's dtype: fp32 masters, 16-bit operand copies)
-                setattr(eng, attr, getattr(eng, attr).to(probe.device))
-            eng._ws, eng._ws_batch, eng._weights_version = None, -1, None
-            for (name, off, numel, shape), (_, p) in zip(eng.entries, self._plist):
-                p.data = eng.params[off:off + numel].view(shape)
-        return self
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return _VitFunction.apply(x, self, *[p for _, p in self._plist])
@@ -407,17 +299,6 @@ def _gelu(u):
 
 def _gelu_grad(u):
     return 0.5 * (1.0 + torch.erf(u * 0.7071067811865476)) + u * torch.exp(-0.5 * u * u) * 0.3989422804014327
-
-
-def _pad4(t: torch.Tensor) -> torch.Tensor:
-    """zero-pad the contraction (last) dim to a multiple of 4 (16-byte rows for the fp32 GEMM)"""
-    k = t.shape[-1]
-    return t.contiguous() if k % 4 == 0 else torch.nn.functional.pad(t, (0, 4 - k % 4)).contiguous()
-
-
-def _wgrad_f32(dy: torch.Tensor, x: torch.Tensor, be) -> torch.Tensor:
-    """dW [out, in] = dy^T x for [rows, out] / [rows, in] fp32 operands with few rows (the pooled [B, D] tail): fp32 MFMA GEMM over the transposed operands"""
-    return ops.gemm_f32(_pad4(dy.t()), _pad4(x.t()), backend=be)
 
 
 class _AttnPoolFn(torch.autograd.Function):
@@ -536,33 +417,12 @@ class AttentionPoolLatent(nn.Module):
                                  self.norm.bias, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.fc2.bias, self)
 
 
-class _LinearFn(torch.autograd.Function):
-    """y = x W^T + b on the fp32 MFMA GEMM (the classifier head on pooled [B, D] rows)"""
-
-    @staticmethod
-    def forward(ctx, x, w, b, be):
-        ctx.save_for_backward(x, w); ctx.be = be
-        return ops.gemm_f32(x.contiguous(), w.detach(), bias=b.detach(), backend=be)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        dy = dy.contiguous()
-        Cn = dy.shape[1]
-        if Cn % 4:      # class counts that are not multiples of 4: zero columns / rows keep the contraction 16-byte aligned
-            dx = ops.gemm_f32(_pad4(dy), torch.nn.functional.pad(w.detach(), (0, 0, 0, 4 - Cn % 4)).contiguous(), b_kmajor=True, backend=ctx.be)
-        else:
-            dx = ops.gemm_f32(dy, w.detach(), b_kmajor=True, backend=ctx.be)
-        return dx, _wgrad_f32(dy, x, ctx.be), dy.sum(0), None
-
-
 class VisionTransformerMap(nn.Module):
     """timm VisionTransformer(class_token=False, global_pool='map', num_classes=C): the vit_*_siglip_* family (BASELINE.json configs[4]).  The trunk is the native
     engine in feature mode without a class token; attn_pool and head run as autograd nodes over the same kernels.  state_dict names equal timm's."""
 
     def __init__(self, spec: VitSpec, device=None, backend: Optional[_lib.Backend] = None, seed: Optional[int] = None, operand: str = "bf16"):
         super().__init__()
-        import dataclasses
         self.spec = spec
         self.num_classes = spec.num_classes
         trunk = VisionTransformer(dataclasses.replace(spec, num_classes=0, class_token=False), device=device, backend=backend, seed=seed, operand=operand)
@@ -629,8 +489,7 @@ class FusedTrainStep:
                  label_smoothing: float = 0.0, max_norm: float = 10.0, ema: bool = True, comm=None, sam: bool = False,
                  sam_rho: float = 0.05, sam_adaptive: bool = True, init_scale: float = 65536.0):
         self.model = model
-        from . import swinv2                     # (here: swinv2 imports swin, which imports this module's names lazily as well)
-        if isinstance(model, swinv2.SwinTransformerV2):
+        if not hasattr(model, "engine"):
             raise NotImplementedError("FusedTrainStep needs a native engine; SwinV2 (swinv2_*_window8_256) is served as autograd nodes over the kernels and trains under a plain "
                                       "torch optimizer over model.parameters() (with a loss scale for fp16 operands).  The native vdk_swinv2_* engine is a follow-up.")
         self.eng = model.engine
@@ -686,7 +545,6 @@ class FusedTrainStep:
         """OHEM-Softmax pre-pass of the reference's loop (engine/procedure/train.py:113-117, structure/sampler.py:11-31): one extra no-grad forward in
         training mode, keep the samples whose target probability is below max(thresh, the min_kept-th smallest); returns the kept (images, labels).
         The batch that reaches step() then changes size from iteration to iteration (workspaces only grow)."""
-        from . import ops
         self.model._sync_flat()
         logits = self.eng.forward(x)
         mask = ops.ohem_mask(logits[:, :self.eng.spec.num_classes].contiguous(), y, min_kept, thresh, ignore_index, backend=self.be)
