@@ -998,7 +998,7 @@ int vdk_gemm_bf16_nt(const GemmDesc* d, void* ws, size_t ws_bytes, void* stream_
 #define LAUNCH256(TNF, EE) LAUNCH256X(TNF, EE, false)
 #define LAUNCH256CS(EE)                                                                                                  \
   do {                                                                                                                   \
-    if (p.colsum_part) VDK_GEMM_LAUNCH((gemm256_bf16_kernel<false, EE, false, true>), grid256, dim3(512));                \
+    if (p.colsum_part) { g_last_kernel = 2; VDK_GEMM_LAUNCH((gemm256_bf16_kernel<false, EE, false, true>), grid256, dim3(512)); }   \
     else LAUNCH256X(false, EE, false);                                                                                   \
   } while (0)
   bool fp16_unserved = false;
