@@ -280,6 +280,9 @@ INTERNAL = {
     "vdk_wa_cos_fwd": (C.c_int, [P, I64, P, I64, P, P, P, P, I32, I64, I32, P, I32, P, SZ, P]),
     "vdk_wa_cos_bwd_workspace_bytes": (C.c_int, [I64, I32, I32, PSZ]),
     "vdk_wa_cos_bwd": (C.c_int, [P, I64, P, P, I64, P, P, P, P, I32, I64, I32, P, P, I64, P, P, I32, P, SZ, P]),
+    "vdk_ls_residual_fwd": (C.c_int, [P, I64, P, I64, P, P, I64, I64, I32, I32, P]),
+    "vdk_ls_residual_bwd_workspace_bytes": (C.c_int, [I64, I32, PSZ]),
+    "vdk_ls_residual_bwd": (C.c_int, [P, I64, P, I64, P, P, I64, P, I64, I32, I32, P, SZ, P]),
 }
 
 

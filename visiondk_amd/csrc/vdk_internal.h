@@ -54,6 +54,14 @@ int vdk_wa_cos_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse
 int vdk_wa_cos_bwd_workspace_bytes(int64_t windows, int32_t nW, int32_t H, size_t* bytes);
 int vdk_wa_cos_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, const float* tau, const float* bias, const float* mask, int32_t nW,
                    int64_t windows, int32_t H, const int32_t* rowidx, void* dqkv, int64_t ldd, float* dbias, float* dtau, int32_t opf, void* ws, size_t ws_bytes, void* stream);
+/* LayerScale on the residual stream (csrc/layerscale_residual.hip; the DINOv2 ViTs): x f32 [rows, ldx], h / dh 16-bit [rows, ldh / lddh] (the branch's last GEMM output and its
+ * gradient; opf 0 = bf16, 1 = fp16), gamma f32 [C].  fwd: y = x + gamma * float(h) (one fp32 multiply, one fp32 add; y may alias x).  bwd: dh = RNE16(gamma * dy) and
+ * dgamma[c] = sum_r dy[r, c] * float(h[r, c]) in fp32, summed in a fixed order through ws and overwritten; the shortcut's gradient is dy itself.  C % 8 == 0, rows >= 1,
+ * pitches >= C and multiples of 8 (16-bit) / 4 (f32), every pointer (ws included) 16-byte aligned: else VDK_EINVAL; another opf VDK_EUNSUPPORTED; a short ws VDK_EWORKSPACE. */
+int vdk_ls_residual_fwd(const float* x, int64_t ldx, const void* h, int64_t ldh, const float* gamma, float* y, int64_t ldy, int64_t rows, int32_t C, int32_t opf, void* stream);
+int vdk_ls_residual_bwd_workspace_bytes(int64_t rows, int32_t C, size_t* bytes);
+int vdk_ls_residual_bwd(const float* dy, int64_t lddy, const void* h, int64_t ldh, const float* gamma, void* dh, int64_t lddh, float* dgamma, int64_t rows, int32_t C, int32_t opf,
+                        void* ws, size_t ws_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

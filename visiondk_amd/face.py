@@ -2,7 +2,7 @@
 `FaceTrainingModel` / `FaceTrainingWrapper`, `FeatureExtractor`, and the `get_model` factory seam.
 
 Reference: models/faceX/backbone/timm_wrapper.py:5-54, models/faceX/face_model.py:10-54,88-143, models/smartmodel.py:5-10.
-Transformer backbones (timm ViT ids in visiondk_amd.vit.TIMM_VITS): neck LayerNorm(C) -> Flatten -> Linear(N*C, feat_dim) ->
+Transformer backbones (timm ViT ids in visiondk_amd.vit.TIMM_VITS, DINOv2 ids in visiondk_amd.dinov2.TIMM_DINOV2S): neck LayerNorm(C) -> Flatten -> Linear(N*C, feat_dim) ->
 BatchNorm1d(feat_dim) (timm_wrapper.py:39-47).  CNN backbones (timm ConvNeXt ids in visiondk_amd.convnext.TIMM_CONVNEXTS): neck
 BatchNorm2d(C) -> Flatten -> Linear(C*H*W, feat_dim) -> BatchNorm1d(feat_dim) (timm_wrapper.py:30-37).  state_dict keys equal the
 reference's: `model.<timm keys>`, `output_layer.0.*` (LayerNorm | BatchNorm2d), `output_layer.2.*` (Linear), `output_layer.3.*`."""
@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _abi, _lib, convnext, heads, ops, resnet, swin, swinv2, vit
+from . import _abi, _lib, convnext, dinov2, heads, ops, resnet, swin, swinv2, vit
 
 
 def _up(x, a):
@@ -249,9 +249,15 @@ class TimmWrapper(nn.Module):
             self.is_cnn = True
             hw, channels = image_size // 32, self.model.num_features
             self.output_layer = nn.Sequential(nn.BatchNorm2d(hw), nn.Flatten(1), nn.Linear(hw * hw * channels, feat_dim), nn.BatchNorm1d(feat_dim)).to(dev)
+        elif model_name in dinov2.TIMM_DINOV2S:
+            # DINOv2 ViT-S/B/L/14 (LayerScale): the normed tokens [B, N, D] go into the transformer neck, as for the native ViTs.  The backbone is the autograd-node form (no
+            # LayerScale mode in the native engine yet): it trains under a torch optimizer, FaceTrainStep and forward_precise refuse it.
+            self.model = dinov2.create_model(model_name, pretrained=False, num_classes=0, global_pool="", img_size=image_size, device=dev, backend=self.be, operand=operand)
+            tokens, channels = self.model.tokens, self.model.spec.dim
+            self.output_layer = nn.Sequential(nn.LayerNorm(channels), nn.Flatten(1), nn.Linear(tokens * channels, feat_dim), nn.BatchNorm1d(feat_dim)).to(dev)
         else:
             raise NotImplementedError(f"backbone '{model_name}': the HIP engines cover {sorted(vit.TIMM_VITS)}, {sorted(convnext.TIMM_CONVNEXTS)} and {sorted(swin.TIMM_SWINS)}"
-                                      f"; as autograd nodes over the kernels: {sorted(swinv2.TIMM_SWINV2S)}")
+                                      f"; as autograd nodes over the kernels: {sorted(swinv2.TIMM_SWINV2S)} and {sorted(dinov2.TIMM_DINOV2S)}")
 
     @torch.no_grad()
     def forward_precise(self, x):
@@ -260,6 +266,8 @@ class TimmWrapper(nn.Module):
         be, ol = self.be, self.output_layer
         if isinstance(self.model, swinv2.SwinTransformerV2):
             raise NotImplementedError(_SWINV2_NEEDS_ENGINE.format(what="forward_precise (fp32-MFMA evaluation)"))
+        if isinstance(self.model, dinov2.DinoVisionTransformer):
+            raise NotImplementedError(dinov2.NEEDS_ENGINE.format(what="forward_precise (fp32-MFMA evaluation)"))
         if not hasattr(self.model, "forward_precise"):
             raise NotImplementedError("forward_precise (fp32-MFMA evaluation) is built for the native ViT, ConvNeXt and Swin engines; this backbone object has none")
         feat = self.model.forward_precise(x)
@@ -421,8 +429,9 @@ class VisionWrapper:
         arch = name[5:].split(".")[0]
         # timm-resnet18 | timm-convnext_* (pet.yaml:21-22) | timm-vit_*
         factory = (resnet.create_model if arch in resnet.TIMM_RESNETS else convnext.create_model if arch in convnext.TIMM_CONVNEXTS else
-                   swin.create_model if arch in swin.TIMM_SWINS else swinv2.create_model if arch.startswith("swinv2_") else vit.create_model)      # timm-swin_base_patch4_window7_224 is pet.yaml:25's default; every
-        #                                                                                     swinv2_ id goes to swinv2.create_model, whose KeyError lists the served window-8 ids
+                   swin.create_model if arch in swin.TIMM_SWINS else swinv2.create_model if arch.startswith("swinv2_") else dinov2.create_model if "dinov2" in arch else vit.create_model)      # timm-swin_base_patch4_window7_224 is pet.yaml:25's default; every
+        #                                                                                     swinv2_ id goes to swinv2.create_model, whose KeyError lists the served window-8 ids; every
+        #                                                                                     dinov2 id likewise to dinov2.create_model (ViT-S/B/L/14 served; giant / reg4 a KeyError)
         self.model = factory(arch, pretrained=False, num_classes=model_cfg["num_classes"], img_size=model_cfg.get("image_size") or 224, device=device,
                              backend=backend, **kwargs)
         if not model_cfg.get("pretrained", False):
@@ -482,6 +491,8 @@ class FaceTrainStep:
             raise NotImplementedError("precision='fp32' with a class-sharded head is not built")
         if isinstance(self.bb.model, swinv2.SwinTransformerV2):
             raise NotImplementedError(_SWINV2_NEEDS_ENGINE.format(what="FaceTrainStep"))
+        if isinstance(self.bb.model, dinov2.DinoVisionTransformer):
+            raise NotImplementedError(dinov2.NEEDS_ENGINE.format(what="FaceTrainStep"))
         if not hasattr(self.bb.model, "engine"):
             raise NotImplementedError("FaceTrainStep needs a backbone with a native engine (ViT, ConvNeXt, Swin with native=True); the autograd-node Swin trains under "
                                       "the reference's own Trainer (torch optimizer over model.parameters())")

@@ -489,6 +489,9 @@ class FusedTrainStep:
                  label_smoothing: float = 0.0, max_norm: float = 10.0, ema: bool = True, comm=None, sam: bool = False,
                  sam_rho: float = 0.05, sam_adaptive: bool = True, init_scale: float = 65536.0):
         self.model = model
+        if type(model).__name__ == "DinoVisionTransformer":
+            from . import dinov2
+            raise NotImplementedError(dinov2.NEEDS_ENGINE.format(what="FusedTrainStep"))
         if not hasattr(model, "engine"):
             raise NotImplementedError("FusedTrainStep needs a native engine; SwinV2 (swinv2_*_window8_256) is served as autograd nodes over the kernels and trains under a plain "
                                       "torch optimizer over model.parameters() (with a loss scale for fp16 operands).  The native vdk_swinv2_* engine is a follow-up.")
