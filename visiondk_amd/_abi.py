@@ -283,6 +283,12 @@ INTERNAL = {
     "vdk_ls_residual_fwd": (C.c_int, [P, I64, P, I64, P, P, I64, I64, I32, I32, P]),
     "vdk_ls_residual_bwd_workspace_bytes": (C.c_int, [I64, I32, PSZ]),
     "vdk_ls_residual_bwd": (C.c_int, [P, I64, P, I64, P, P, I64, P, I64, I32, I32, P, SZ, P]),
+    "vdk_cbir_range_workspace_bytes": (C.c_int, [I64, I64, I32, PSZ]),
+    "vdk_cbir_range_count": (C.c_int, [P, I64, P, I32, P, P, I64, I32, F32, I32, P, P, SZ, P]),
+    "vdk_cbir_range_fill": (C.c_int, [P, I64, P, I32, I64, I32, I64, P, I64, P, P, P, SZ, P]),
+    "vdk_dbscan_core": (C.c_int, [P, I64, I64, P, P, P]),
+    "vdk_dbscan_round": (C.c_int, [P, P, I64, P, P, P, P, P]),
+    "vdk_dbscan_assign": (C.c_int, [P, P, I64, P, P, P, P, P]),
 }
 
 

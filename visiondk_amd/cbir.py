@@ -8,7 +8,7 @@ Mirrors the retrieval seam of the reference (SURVEY.md §8(b) "Retrieval index p
 
 `index_factory(dim, "Flat", METRIC_INNER_PRODUCT)` returns a `FlatIPIndex` with the same methods; numpy in /
 numpy out like faiss, or device tensors in / device tensors out to skip the host round trip.  All arithmetic
-happens in the HIP kernels of csrc/cbir.hip through the C ABI; there is no CPU fallback.
+happens in the HIP kernels of csrc/cbir.hip (top-k `search`) and csrc/cbir_range.hip (`range_search`) through the C ABI; there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -25,6 +25,7 @@ DEFAULT_CAP = 131072      # candidate-list capacity per query of the GUARANTEED 
                           # round 6 (approximate ranking): 32 k 3.85 ms, 48 k 3.53, 64 k 3.40, 96 k 3.30, 128 k 3.23, 192 k 3.25 (fewer launches against looser
                           # thresholds per stage; round 3's exact ranking: 96 k 3.54, 128 k 3.53); with small_lists the lists hold SMALL_LIST_CAP entries
 SMALL_LIST_CAP = 16384    # staged schedule with small candidate lists (`small_lists=True`): stages of cap - k rows like the guaranteed schedule, lists of this many entries
+RANGE_MASK_BYTES = 1 << 30  # range_search: bound of the one-bit-per-pair matrix of a query block (nq N / 8 bytes: 8192 queries per block against 10^6 rows)
 OPTIMISTIC_CAP = 8192     # ... of the optimistic schedule (bootstrap + two stages; ~10^3 survivors per query in a 10^6-row scan; overflow is detected and repaired)
 
 
@@ -221,6 +222,61 @@ class FlatIPIndex:
         if as_numpy:
             return scores.cpu().numpy(), idx.cpu().numpy()
         return scores, idx
+
+    def range_search(self, q, thresh: float, inclusive: bool = False, max_results: Optional[int] = None):
+        """faiss IndexFlat.range_search(x, thresh) -> (lims int64 [nq + 1], D float32 [lims[nq]], I int64 [lims[nq]]): query i owns entries [lims[i], lims[i + 1]), every gallery
+        row whose EXACT score (the k-ordered fp32 fmaf chain `search` ranks on) is > thresh (faiss's rule for inner product), or >= thresh with inclusive=True; inside a query
+        the rows come in ascending index (faiss leaves the order open).  numpy in -> numpy out; tensor in -> tensors on the device.  csrc/cbir_range.hip: one bit per pair, so
+        no result size can overflow anything; the queries are processed in blocks that keep that bit matrix under RANGE_MASK_BYTES, with one host read (a block's total) each.
+        max_results: a RuntimeError carrying the exact total when it exceeds this, raised before any output larger than max_results exists."""
+        if self.method != "prefilter":
+            raise NotImplementedError("range_search is served for d <= 512 on the prefilter path; the exact-scan form (d > 512 or method=\"exact_scan\") is not built")
+        thresh = float(np.float32(thresh))
+        if thresh != thresh:
+            raise ValueError("range_search: the threshold is NaN")
+        as_numpy = isinstance(q, np.ndarray)
+        qd = self._to_dev(q)
+        g = self._materialize()
+        self._prepare()
+        if self.storage == "float16":
+            qd = qd.half().float()                    # as search(): fp16 x fp16 products, fp32 accumulation
+        from . import _abi
+        be, nq, n = self.be, qd.shape[0], g.shape[0]
+        gdt = _abi.F16_ if self.storage == "float16" else _abi.F32_
+        words = (n + 31) // 32
+        qblk = max(512, RANGE_MASK_BYTES // max(4 * words, 1) // 512 * 512)          # queries per call: whole 512-query workgroups
+        lims_parts, d_parts, i_parts, total = [], [], [], 0
+        for q0 in range(0, max(nq, 1), qblk):
+            qb = qd[q0:q0 + qblk]
+            nb = qb.shape[0]
+            need = C.c_size_t(0)
+            be.check(be.lib.vdk_cbir_range_workspace_bytes(nb, n, self._dp, C.byref(need)), "vdk_cbir_range_workspace_bytes")
+            if self._ws is None or self._ws.numel() < need.value:
+                self._ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            ws = self._ws
+            lims = torch.empty(nb + 1, dtype=torch.int64, device=self.device)
+            be.check(be.lib.vdk_cbir_range_count(be.ptr(qb) if nb else None, nb, be.ptr(g) if n else None, gdt, be.ptr(self._gb), be.ptr(self._gmax), n, self._dp, thresh,
+                                                 int(bool(inclusive)), be.ptr(lims), be.ptr(ws), ws.numel(), be.stream()), "vdk_cbir_range_count")
+            tb = int(lims[nb].item())                 # the one host read of this block
+            lims_parts.append(lims[:nb] + total)
+            total += tb
+            if max_results is not None and total > max_results:
+                continue                              # keep counting (the message states the exact total), write nothing more
+            ds = torch.empty(tb, dtype=torch.float32, device=self.device)
+            ix = torch.empty(tb, dtype=torch.int64, device=self.device)
+            be.check(be.lib.vdk_cbir_range_fill(be.ptr(qb) if nb else None, nb, be.ptr(g) if n else None, gdt, n, self._dp, self.idx_base, be.ptr(lims), tb,
+                                                be.ptr(ds) if tb else None, be.ptr(ix) if tb else None, be.ptr(ws), ws.numel(), be.stream()), "vdk_cbir_range_fill")
+            d_parts.append(ds)
+            i_parts.append(ix)
+        if max_results is not None and total > max_results:
+            raise RuntimeError(f"range_search: {total} results exceed max_results = {max_results}")
+        lims_parts.append(torch.tensor([total], dtype=torch.int64, device=self.device))
+        lims = torch.cat(lims_parts)
+        ds = d_parts[0] if len(d_parts) == 1 else torch.cat(d_parts)
+        ix = i_parts[0] if len(i_parts) == 1 else torch.cat(i_parts)
+        if as_numpy:
+            return lims.cpu().numpy(), ds.cpu().numpy(), ix.cpu().numpy()
+        return lims, ds, ix
 
 
 def fp16_swap_report(scores32: np.ndarray, idx32: np.ndarray, idx16: np.ndarray) -> dict:

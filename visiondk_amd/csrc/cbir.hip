@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include "vdk_device.h"
 #include "vdk_host.h"
+#include "cbir_device.h"   // cbir_exact_ip*, cbir_eps
 
 #define CB_BQ 128        // queries per workgroup
 #define CB_BG 128        // gallery rows per tile
@@ -285,58 +286,6 @@ __global__ __launch_bounds__(256) void cbir_select_kernel(CbirCand cand, long nq
 // [carry[q], cnt[q]) hold only an index and get the oracle's k-ordered fmaf chain here).  A wave sorts up to CW_KEYS keys
 // in its own 8 KB LDS region with wave-synchronous bitonic steps (no workgroup barriers), so 20 waves per CU hide each
 // other's global-latency chains; typical steady-state input is k carried keys + ~10 new ones.
-// the oracle's score of one pair: k-ordered fmaf chain from +0 (oracle/cbir_oracle.c oracle_ip_pair), loads batched 8 deep
-__device__ __forceinline__ float cbir_exact_ip(const float* __restrict__ qrow, const float* __restrict__ g, int D) {
-  float acc = 0.f;
-  int c = 0;
-  for (; c + 32 <= D; c += 32) {
-    f32x4 gv[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) gv[j] = *(const f32x4*)(g + c + 4 * j);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const f32x4 qv = *(const f32x4*)(qrow + c + 4 * j);
-      acc = fmaf(qv[0], gv[j][0], acc); acc = fmaf(qv[1], gv[j][1], acc); acc = fmaf(qv[2], gv[j][2], acc); acc = fmaf(qv[3], gv[j][3], acc);
-    }
-  }
-  for (; c < D; c += 4) {
-    const f32x4 gv = *(const f32x4*)(g + c);
-    const f32x4 qv = *(const f32x4*)(qrow + c);
-    acc = fmaf(qv[0], gv[0], acc); acc = fmaf(qv[1], gv[1], acc); acc = fmaf(qv[2], gv[2], acc); acc = fmaf(qv[3], gv[3], acc);
-  }
-  return acc + 0.0f;
-}
-
-// the same chain over a gallery row STORED in fp16 (faiss GpuClonerOptions.useFloat16, engine/cbir/evaluation.py:157-162): every element converts exactly to
-// fp32, so the score equals cbir_exact_ip on the fp16-rounded row
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ float cbir_exact_ip_h(const float* __restrict__ qrow, const _Float16* __restrict__ g, int D) {
-  float acc = 0.f;
-  int c = 0;
-  for (; c + 64 <= D; c += 64) {          // loads batched 8 deep like the fp32 chain (the chain itself is latency-bound, the loads must not be)
-    f16x8_t gv[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) gv[j] = *(const f16x8_t*)(g + c + 8 * j);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const f32x4 q0 = *(const f32x4*)(qrow + c + 8 * j), q1 = *(const f32x4*)(qrow + c + 8 * j + 4);
-      acc = fmaf(q0[0], (float)gv[j][0], acc); acc = fmaf(q0[1], (float)gv[j][1], acc); acc = fmaf(q0[2], (float)gv[j][2], acc); acc = fmaf(q0[3], (float)gv[j][3], acc);
-      acc = fmaf(q1[0], (float)gv[j][4], acc); acc = fmaf(q1[1], (float)gv[j][5], acc); acc = fmaf(q1[2], (float)gv[j][6], acc); acc = fmaf(q1[3], (float)gv[j][7], acc);
-    }
-  }
-  for (; c + 8 <= D; c += 8) {
-    const f16x8_t gv = *(const f16x8_t*)(g + c);
-    const f32x4 q0 = *(const f32x4*)(qrow + c), q1 = *(const f32x4*)(qrow + c + 4);
-    acc = fmaf(q0[0], (float)gv[0], acc); acc = fmaf(q0[1], (float)gv[1], acc); acc = fmaf(q0[2], (float)gv[2], acc); acc = fmaf(q0[3], (float)gv[3], acc);
-    acc = fmaf(q1[0], (float)gv[4], acc); acc = fmaf(q1[1], (float)gv[5], acc); acc = fmaf(q1[2], (float)gv[6], acc); acc = fmaf(q1[3], (float)gv[7], acc);
-  }
-  for (; c < D; ++c) acc = fmaf(qrow[c], (float)g[c], acc);
-  return acc + 0.0f;
-}
-// G: fp32 rows, or fp16 rows when g_half
-__device__ __forceinline__ float cbir_exact_ip_any(const float* __restrict__ qrow, const float* __restrict__ G, long row, int D, int g_half) {
-  return g_half ? cbir_exact_ip_h(qrow, (const _Float16*)G + row * (long)D, D) : cbir_exact_ip(qrow, G + row * (long)D, D);
-}
 
 #define CW_KEYS 512
 __global__ __launch_bounds__(256) void cbir_rank_wave_kernel(const float* __restrict__ Q, const float* __restrict__ G, int D, long idx_base,
@@ -521,14 +470,6 @@ __global__ __launch_bounds__(256) void cbir_max3_kernel(const float* __restrict_
   }
 }
 __global__ void cbir_gstat_init_kernel(unsigned* __restrict__ bits, unsigned chunks) { if (threadIdx.x < 4) bits[threadIdx.x] = threadIdx.x == 3 ? chunks : 0u; }
-// eps_q of the header comment
-// (the accumulation term scales with the contraction length: 4e-5 covers 128 terms with a 5x margin, gstat_bits[3] holds DP / 128)
-__device__ __forceinline__ float cbir_eps(const float* __restrict__ qn3, long q, const unsigned* __restrict__ gstat_bits) {
-  const float gt = __uint_as_float(gstat_bits[1]), ge = __uint_as_float(gstat_bits[2]);
-  const float qn = qn3[q * 3], qt = qn3[q * 3 + 1], qe = qn3[q * 3 + 2];
-  const float len = gstat_bits[3] > 1u ? (float)gstat_bits[3] : 1.0f;
-  return 1.00001f * (qe * gt + qn * ge) + 4e-5f * len * qt * gt;
-}
 
 // grid: id -> split = id % nsplit, qblock = id / nsplit.  512 threads = 8 waves; wave w owns 64 queries (two 32-wide column
 // tiles whose bf16 fragments stay in 64 VGPRs for the whole scan) and scores them against all 128 rows of every gallery
@@ -1130,6 +1071,10 @@ static void cb_launch_prefilter(hipStream_t stream, int DP, unsigned grid, const
     case 384: hipLaunchKernelGGL((cbir_prefilter_wide_kernel<BOOT, 24>), dim3(grid), dim3(512), 0, stream, Qb, qnorm, nq, Gb, gmax_bits, begin, end, rps, nsplit, idx_base, thr, cand, gm, gm_ld); break;
     default: hipLaunchKernelGGL((cbir_prefilter_wide_kernel<BOOT, 32>), dim3(grid), dim3(512), 0, stream, Qb, qnorm, nq, Gb, gmax_bits, begin, end, rps, nsplit, idx_base, thr, cand, gm, gm_ld); break;
   }
+}
+
+void vdk_cbir_cast_rows(const float* x, long n, int D, int DP, bf16_t* xb, float* norms3, void* stream) {   // (cbir_device.h)
+  hipLaunchKernelGGL(cbir_cast_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, n, D, DP, xb, norms3);
 }
 
 // ------------------------------------------------------------------------------------ host side

@@ -62,6 +62,27 @@ int vdk_ls_residual_fwd(const float* x, int64_t ldx, const void* h, int64_t ldh,
 int vdk_ls_residual_bwd_workspace_bytes(int64_t rows, int32_t C, size_t* bytes);
 int vdk_ls_residual_bwd(const float* dy, int64_t lddy, const void* h, int64_t ldh, const float* gamma, void* dh, int64_t lddh, float* dgamma, int64_t rows, int32_t C, int32_t opf,
                         void* ws, size_t ws_bytes, void* stream);
+/* Exact range search (csrc/cbir_range.hip; faiss IndexFlat.range_search): every gallery row whose exact score -- the k-ordered fp32 fmaf chain of vdk_cbir_search -- passes
+ * `radius` (s > radius, or s >= radius when inclusive), per query in ascending row order.  Q f32 [nq, D]; G f32 or fp16 (g_dtype VDK_F32 / VDK_F16) [N, D]; Gb / gmax_bits from
+ * vdk_cbir_prepare_gallery.  Two calls with one host read between them, both on the same workspace (vdk_cbir_range_workspace_bytes(nq, N, D), untouched in between):
+ *   vdk_cbir_range_count  -> lims int64 [nq + 1] (device): query i owns entries [lims[i], lims[i + 1]) of the result;
+ *   vdk_cbir_range_fill   -> out_scores f32 [total], out_idx int64 [total] = idx_base + row, with total = lims[nq] as the host read it; nothing past `total` is written.
+ * No capacity, no overflow, no retry: the workspace holds one bit per pair.  D % 4 (fp16 rows: % 8), D <= 512, a NaN radius, a null output with total > 0: VDK_EINVAL;
+ * a short workspace: VDK_EWORKSPACE.  nq == 0 and N == 0 are served (lims all zero) and need no workspace. */
+int vdk_cbir_range_workspace_bytes(int64_t nq, int64_t N, int32_t D, size_t* bytes);
+int vdk_cbir_range_count(const float* Q, int64_t nq, const void* G, int32_t g_dtype, const void* Gb, const uint32_t* gmax_bits, int64_t N, int32_t D, float radius,
+                         int32_t inclusive, int64_t* lims, void* ws, size_t ws_bytes, void* stream);
+int vdk_cbir_range_fill(const float* Q, int64_t nq, const void* G, int32_t g_dtype, int64_t N, int32_t D, int64_t idx_base, const int64_t* lims, int64_t total, float* out_scores,
+                        int64_t* out_idx, const void* ws, size_t ws_bytes, void* stream);
+/* DBSCAN on a neighbourhood CSR (lims int64 [n + 1], nbr int64 [lims[n]] with values in [0, n); the point itself is a member of its neighbourhood), n < 2^31:
+ *   vdk_dbscan_core    core[i] = |N(i)| >= min_samples; label[i] = i for a core point, -1 otherwise;
+ *   vdk_dbscan_round   one round label_out[i] = label_in[min over i and its core neighbours j of label_in[j]] for the core points (two distinct buffers); *changed (device u32,
+ *                      cleared by the caller) is set when any label moved.  Repeated until it stays clear, a core point's label is its component's smallest core index;
+ *   vdk_dbscan_assign  out[i] = rank[label[i]] for a core point, the smallest rank[label[j]] among the core neighbours j of any other point, or -1; rank int32 [n] = exclusive
+ *                      prefix sum of (core[i] && label[i] == i), formed by the caller. */
+int vdk_dbscan_core(const int64_t* lims, int64_t n, int64_t min_samples, uint8_t* core, int32_t* label, void* stream);
+int vdk_dbscan_round(const int64_t* lims, const int64_t* nbr, int64_t n, const uint8_t* core, const int32_t* label_in, int32_t* label_out, uint32_t* changed, void* stream);
+int vdk_dbscan_assign(const int64_t* lims, const int64_t* nbr, int64_t n, const uint8_t* core, const int32_t* label, const int32_t* rank, int64_t* out, void* stream);
 #ifdef __cplusplus
 }
 #endif
