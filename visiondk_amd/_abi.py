@@ -270,6 +270,9 @@ INTERNAL = {
     "vdk_gemm_debug_stamps": (C.c_int, [P]),
     "vdk_attention_force_legacy": (C.c_int, [I32]),
     "vdk_debug_reduce_rows_job": (C.c_int, [P, I64, I32, I64, P, F32, P]),
+    "vdk_debug_layernorm_bwd_forms": (C.c_int, [P, I64, I32, P, I64, P, P, P, P, I64, I32, I32, P, I64, P, I64, P, P, P, SZ, P,
+                                                P, P, I64, I32, P, P, I32, P, P, I32, P, I32]),
+    "vdk_debug_colsum16_q8": (C.c_int, [P, I64, I32, I32, P, P, SZ, P, I64, I32, P, P, I32, P]),
     "vdk_debug_attention_cls_fwd": (C.c_int, [P, I64, P, I64, P, I32, I32, I32, I32, F32, I32, I32, P]),
     "vdk_debug_attention_cls_bwd": (C.c_int, [P, I64, P, P, I64, P, P, I64, P, I32, I32, I32, I32, F32, I32, I32, P]),
     "vdk_debug_attention_hd_fwd": (C.c_int, [P, I64, P, I64, P, I32, I32, I32, I32, F32, I32, P]),

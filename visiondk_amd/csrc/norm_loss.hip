@@ -896,4 +896,26 @@ extern "C" int vdk_debug_reduce_rows_job(float* buf, int64_t ld, int32_t S, int6
   const VdkReduceJob jb = {buf, (long)ld, (int)S, (long)n, out, scale};
   return vdk_reduce_rows_batch(&jb, 1, stream);
 }
+/* tests: vdk_layernorm_bwd_deferred as the engines call it, then the jobs it handed back (dgamma | dbeta, 2C wide; the column sums, C wide) in one vdk_reduce_rows_batch.
+   Nothing is routed, repaired or refused here: every argument goes through as it came, and the callee's code comes back as it is. */
+extern "C" int vdk_debug_layernorm_bwd_forms(const void* dy, int64_t lddy, int32_t dy_dtype, const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
+                                             const float* dres, int64_t lddres, int32_t T, int32_t C, float* dx, int64_t lddx, void* dxb, int64_t lddxb, float* dgamma,
+                                             float* dbeta, void* ws, size_t ws_bytes, void* stream, float* dxb_colsum, void* out8, int64_t ldo8, int32_t fmt, const float* scale,
+                                             float* amax, int32_t opf, const float* dy_scale, const float* dxb_rs, int32_t dxb_rps, const void* dres16, int32_t deferred) {
+  VdkReduceJob jobs[2] = {VdkReduceJob{nullptr, 0, 0, 0, nullptr, 1.0f}, VdkReduceJob{nullptr, 0, 0, 0, nullptr, 1.0f}};
+  const LnQ8 q8 = {(unsigned char*)out8, (long)ldo8, scale, amax, (int)fmt};
+  const int rc = vdk_layernorm_bwd_deferred(dy, lddy, dy_dtype, x, ldx, mean, rstd, gamma, dres, lddres, T, C, dx, lddx, dxb, lddxb, dgamma, dbeta, ws, ws_bytes, stream,
+                                            deferred ? &jobs[0] : nullptr, dxb_colsum, &jobs[1], out8 ? &q8 : nullptr, (int)opf, dy_scale, dxb_rs, (int)dxb_rps, dres16);
+  if (rc != VDK_OK) return rc;
+  return vdk_reduce_rows_batch(jobs, 2, stream);
+}
+/* tests: vdk_colsum_bf16_deferred (16-bit input of format opf, optional fp8 copy out8 [T, ldo8] with its amax), then its job through vdk_reduce_rows_batch */
+extern "C" int vdk_debug_colsum16_q8(const void* in, int64_t ld, int32_t T, int32_t N, float* out, void* ws, size_t ws_bytes, void* out8, int64_t ldo8, int32_t fmt,
+                                     const float* scale, float* amax, int32_t opf, void* stream) {
+  VdkReduceJob job = {nullptr, 0, 0, 0, nullptr, 1.0f};
+  const LnQ8 q8 = {(unsigned char*)out8, (long)ldo8, scale, amax, (int)fmt};
+  const int rc = vdk_colsum_bf16_deferred(in, ld, T, N, out, ws, ws_bytes, stream, &job, out8 ? &q8 : nullptr, (int)opf);
+  if (rc != VDK_OK) return rc;
+  return vdk_reduce_rows_batch(&job, 1, stream);
+}
 

@@ -25,6 +25,20 @@ int vdk_gemm_debug_stamps(void* device_u64_buffer);
 int vdk_attention_force_legacy(int32_t on);
 /* tests: one job of the batched row reduction (vdk_reduce_rows_batch) */
 int vdk_debug_reduce_rows_job(float* buf, int64_t ld, int32_t S, int64_t n, float* out, float scale, void* stream);
+/* TEST-ONLY (tests/test_layernorm_forms.py): the forms of the LayerNorm backward that only the engines reach (csrc/norm_loss.hip, vdk_layernorm_bwd_deferred).  The first 21
+ * arguments are those of vdk_layernorm_bwd; then dxb_colsum f32 [C] or NULL (column sums of the stored dxb); the fp8 copy of dxb: out8 [T, ldo8] bytes or NULL (= none), fmt
+ * 0 = e4m3 / 1 = e5m2, scale and amax f32 device scalars; opf = format of dxb for an fp32 dy (0 = bf16, 1 = fp16); dy_scale f32 device scalar or NULL; dxb_rs f32
+ * [ceil(T / dxb_rps)] or NULL (factor of the 16-bit copy only); dres16 = the residual gradient as fp16 rows (pitch lddres) or NULL; deferred != 0: the dgamma | dbeta reduction
+ * is left to the caller's job.  Everything is forwarded unchanged and the jobs that come back run in ONE vdk_reduce_rows_batch; a refusal of the callee is returned as it is.
+ * ws: vdk_layernorm_bwd_workspace_bytes(T, C). */
+int vdk_debug_layernorm_bwd_forms(const void* dy, int64_t lddy, int32_t dy_dtype, const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
+                                  const float* dres, int64_t lddres, int32_t T, int32_t C, float* dx, int64_t lddx, void* dxb, int64_t lddxb, float* dgamma, float* dbeta,
+                                  void* ws, size_t ws_bytes, void* stream, float* dxb_colsum, void* out8, int64_t ldo8, int32_t fmt, const float* scale, float* amax,
+                                  int32_t opf, const float* dy_scale, const float* dxb_rs, int32_t dxb_rps, const void* dres16, int32_t deferred);
+/* TEST-ONLY: vdk_colsum_bf16_deferred (16-bit `in` [T, ld] of format opf; out f32 [N]; optional fp8 copy out8 [T, ldo8] bytes of a bf16 input with its amax, NULL = none) and
+ * its job through vdk_reduce_rows_batch.  ws: vdk_colsum_bf16_workspace_bytes(T, N). */
+int vdk_debug_colsum16_q8(const void* in, int64_t ld, int32_t T, int32_t N, float* out, void* ws, size_t ws_bytes, void* out8, int64_t ldo8, int32_t fmt, const float* scale,
+                          float* amax, int32_t opf, void* stream);
 /* tests: the class-query attention kernels of csrc/attention_cls.hip on their own (the ViT engine reaches them in-library).  Tensors as for vdk_attention_fwd_dt /
  * vdk_attention_bwd_dt, but only row b * N of q, o, dout, dq and lse[(b * H + h) * N] are touched; cspart: f32 [B][3 * H * head_dim] or NULL; grid: workgroups, 0 = default */
 int vdk_debug_attention_cls_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, int32_t B, int32_t N, int32_t H, int32_t head_dim, float scale, int32_t dtype,
