@@ -292,6 +292,9 @@ INTERNAL = {
     "vdk_dbscan_core": (C.c_int, [P, I64, I64, P, P, P]),
     "vdk_dbscan_round": (C.c_int, [P, P, I64, P, P, P, P, P]),
     "vdk_dbscan_assign": (C.c_int, [P, P, I64, P, P, P, P, P]),
+    "vdk_mst_scan_workspace_bytes": (C.c_int, [I64, I64, I32, PSZ]),
+    "vdk_mst_scan_mask_layout": (C.c_int, [I64, I64, I32, PSZ, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "vdk_mst_scan": (C.c_int, [P, P, P, P, P, P, I64, I32, I64, I64, P, P, P, SZ, P]),
 }
 
 

@@ -97,6 +97,18 @@ int vdk_cbir_range_fill(const float* Q, int64_t nq, const void* G, int32_t g_dty
 int vdk_dbscan_core(const int64_t* lims, int64_t n, int64_t min_samples, uint8_t* core, int32_t* label, void* stream);
 int vdk_dbscan_round(const int64_t* lims, const int64_t* nbr, int64_t n, const uint8_t* core, const int32_t* label_in, int32_t* label_out, uint32_t* changed, void* stream);
 int vdk_dbscan_assign(const int64_t* lims, const int64_t* nbr, int64_t n, const uint8_t* core, const int32_t* label, const int32_t* rank, int64_t* out, void* stream);
+/* One Boruvka round's row scan over the cosine mutual-reachability graph (csrc/cbir_mst.hip; HDBSCAN's minimum spanning tree).  X f32 [N, D] = the unit rows; Gb bf16
+ * [N, DP], gnorm f32 [3 N] and gmax_bits = the three outputs of vdk_cbir_prepare_gallery(X, N, D); core f32 [N] (>= 0); comp int32 [N] (>= 0: the component of every row).
+ * For every row i of the block [q0, q0 + nq):  best_j[i] = the partner j with comp[j] != comp[i] of the smallest key (w_ij, j), w_ij = max(core_i, core_j, max(0, 1.0f - s_ij))
+ * on the exact score s_ij (the k-ordered fp32 fmaf chain of vdk_cbir_search), best_w[i] = that w_ij; (+inf, -1) when every row shares comp[i].  Nothing outside the block is
+ * written.  The same bits on every run: a bf16-MFMA bound pass and propose pass (one bit per pair in the workspace) only select the pairs that get the exact chain.
+ * D % 4, D > 512, N < 2, N >= 2^31, a block outside [0, N), a null or misaligned pointer (X, Gb, ws: 16 bytes; the others 4): VDK_EINVAL; a short workspace
+ * (vdk_mst_scan_workspace_bytes(nq, N, D)): VDK_EWORKSPACE. */
+int vdk_mst_scan_workspace_bytes(int64_t nq, int64_t N, int32_t D, size_t* bytes);
+/* tools: where a scan of this shape leaves its one-bit-per-pair matrix in the workspace: uint32 word [b * pitch_words + q] at offset_bytes, b < blocks, q < nq */
+int vdk_mst_scan_mask_layout(int64_t nq, int64_t N, int32_t D, size_t* offset_bytes, int64_t* pitch_words, int64_t* blocks);
+int vdk_mst_scan(const float* X, const void* Gb, const float* gnorm, const uint32_t* gmax_bits, const float* core, const int32_t* comp, int64_t N, int32_t D, int64_t q0,
+                 int64_t nq, float* best_w, int32_t* best_j, void* ws, size_t ws_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif
