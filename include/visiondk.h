@@ -487,8 +487,19 @@ int vdk_im2col_bf16(const void* in, void* col, int32_t B, int32_t H, int32_t W, 
                     void* stream);
 /* nn.BatchNorm2d on NHWC rows x f32 [R, C] fused with the BasicBlock tail: out = [relu](bn(x) [+ res]) as bf16 and / or f32; res f32 or bf16.
  * Backward (training mode): dout f32 = gradient of out, out_bf16 = out (ReLU mask, NULL = no ReLU) -> dy_bf16 (gradient of x, the conv GEMMs' operand),
- * dres f32 (gradient of res = masked dout, optional), dgamma, dbeta.  sync != NULL turns both into SyncBatchNorm: forward all-reduces (sum x, sum x^2, count),
- * backward (sum g, sum g x^, count); dgamma / dbeta stay local sums like torch.nn.SyncBatchNorm (the gradient all-reduce follows). */
+ * dres f32 (gradient of res = masked dout, optional), dgamma, dbeta.  sync != NULL turns both into SyncBatchNorm: forward all-reduces
+ * (sum (x - K), sum (x - K)^2, count) [2C + 1] with K[c] = running_mean[c] as it stands BEFORE this call's update (0 where running_mean is NULL): the running
+ * statistics are equal on every rank, so a plain SUM over the ranks still combines the vector.  THE CALLER KEEPS THEM EQUAL: with running_mean differing between
+ * ranks (a checkpoint loaded on one rank only, a per-rank training forward outside the group) the summed moments refer to different K and the variance is wrong
+ * without any error -- load and broadcast the buffers on every rank, as DistributedDataParallel does.  Backward all-reduces (sum g, sum g x^, count) as before;
+ * dgamma / dbeta stay local sums like torch.nn.SyncBatchNorm (the gradient all-reduce follows).
+ * Accuracy of the batch statistics (one read of x, fixed combination order, bit-reproducible): without sync the variance is centred (per-slice moments about the
+ * slice's first row k, combined in fp64; a slice whose mean^2 <= 9 variance keeps its raw moments, and a channel made of such slices the bits of save_mean and
+ * save_invstd it always had -- running_var, now formed from the fp32 variance, may move by one ulp).  A shifted slice loses about (1 + ((k - mean) / sigma)^2)
+ * x 2^-24 of its variance: a few 2^-24 of save_invstd wherever the channel's mean lies when the first row is an ordinary one, ten times that in a slice whose
+ * first row is a 4-sigma outlier (one slice's share of the channel only).  With sync the fp32 vector holds moments about K, so
+ * the variance loses about (1 + ((mean - K) / sigma)^2) x 2^-24 of itself: the same few 2^-24 once running_mean has come near the batch mean (a warmed-up module),
+ * and on a cold start (running_mean = 0) what the raw moments E[x^2] - E[x]^2 give: (mean / sigma)^2 x 2^-24, i.e. 1e-3 at a mean of 100 sigma. */
 /* SyncBatchNorm hook (the reference's opt-in, engine/vision_engine.py:224-225): called on the host with a device vector of n floats whose producer kernel is
  * already enqueued on `stream`; the callee enqueues a SUM all-reduce of it over the data-parallel ranks, ordered before later work on `stream`. */
 typedef void (*vdk_stat_sync_fn)(void* user, float* stats, int64_t n);

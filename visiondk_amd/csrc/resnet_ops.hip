@@ -74,20 +74,26 @@ __global__ __launch_bounds__(256) void im2col_bf16_kernel(const bf16_t* __restri
 
 // ------------------------------------------------------------------------------------ BatchNorm2d on NHWC rows
 // statistics: grid (S slices, ceil(C / 64)); 512 threads = 64 columns x 8 row groups; a slice owns rows [s*rps, (s+1)*rps)
-// MODE 0: (sum x, sum x^2);  MODE 1 (backward): g = dout * (relu ? out > 0 : 1): (sum g, sum g * xhat)
+// MODE 0: the raw moments (sum x, sum x^2) AND the moments about k = the slice's own first row of the column, (sum d, sum d^2) with d = x - k, in one read of x.
+//   sum x^2 / R - mean^2 in fp32 loses (mean / sigma)^2 x 2^-24 of the variance (10 % at a mean of 1000 sigma), while |d| stays within a few standard deviations
+//   wherever the mean lies.  A slice whose own mean^2 <= 9 variance (judged from the shifted pair) stores the raw pair, marked by the sign of the second entry
+//   (-sum x^2; -0 counts): there the raw moments lose at most (1 + 9) x 2^-24 of the variance, 5 x 2^-24 of invstd, and such a column keeps the arithmetic, and
+//   the bits, it always had.  Every other slice stores the shifted pair; bn_combine_fwd_kernel re-reads its k.
+// MODE 1 (backward): g = dout * (relu ? out > 0 : 1): (sum g, sum g * xhat)
 template <int MODE>
 __global__ __launch_bounds__(512) void bn_partial_kernel(const float* __restrict__ x, const float* __restrict__ dout, const bf16_t* __restrict__ outb,
                                                          const float* __restrict__ mean, const float* __restrict__ invstd, long R, int C, long rps,
                                                          float* __restrict__ part /*[S][2][C]*/, int opf) {
-  __shared__ float red[2][8][64];
+  __shared__ float red[MODE ? 2 : 4][8][64];
   const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6, c = blockIdx.y * 64 + cl;
   const long r0 = (long)blockIdx.x * rps;
   long r1 = r0 + rps; if (r1 > R) r1 = R;
-  float a0 = 0.f, a1 = 0.f;
+  float a0 = 0.f, a1 = 0.f, s0 = 0.f, s1 = 0.f, k = 0.f;
   if (c < C) {
     const float mu = MODE ? mean[c] : 0.f, is = MODE ? invstd[c] : 0.f;
+    if (MODE == 0 && r0 < r1) k = x[r0 * C + c];
     for (long r = r0 + rg; r < r1; r += 8) {
-      if (MODE == 0) { const float v = x[r * C + c]; a0 += v; a1 = fmaf(v, v, a1); }
+      if (MODE == 0) { const float v = x[r * C + c], d = v - k; a0 += v; a1 = fmaf(v, v, a1); s0 += d; s1 = fmaf(d, d, s1); }
       else {
         float g = dout[r * C + c];
         if (outb && !(rn_from16(outb[r * C + c], opf) > 0.f)) g = 0.f;
@@ -96,8 +102,22 @@ __global__ __launch_bounds__(512) void bn_partial_kernel(const float* __restrict
     }
   }
   red[0][rg][cl] = a0; red[1][rg][cl] = a1;
+  if (MODE == 0) { red[2][rg][cl] = s0; red[3][rg][cl] = s1; }
   __syncthreads();
-  if (rg < 2 && c < C) {
+  if (MODE == 0) {
+    if (rg == 0 && c < C) {
+      float t[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) t[j] += red[j][i][cl];
+      const float n = (float)(r1 > r0 ? r1 - r0 : 1);
+      const float md = t[2] / n, ms = k + md, vs = t[3] / n - md * md;
+      const bool raw = ms * ms <= 9.f * vs;
+      part[((long)blockIdx.x * 2) * C + c] = raw ? t[0] : t[2];
+      part[((long)blockIdx.x * 2 + 1) * C + c] = raw ? -t[1] : t[3];
+    }
+  } else if (rg < 2 && c < C) {
     float t = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) t += red[rg][i][cl];
@@ -126,17 +146,72 @@ __global__ __launch_bounds__(256) void bn_combine_kernel(const float* __restrict
     sums[i] = (float)t;
   }
 }
-// forward finalize from sums (sum x, sum x^2, count): mean / biased var -> invstd, running statistics (unbiased var); eval mode: running statistics
-__global__ __launch_bounds__(256) void bn_finalize_fwd_kernel(const float* __restrict__ sums, int C, float eps, float momentum, int training, float* __restrict__ rmean,
-                                                              float* __restrict__ rvar, float* __restrict__ save_mean, float* __restrict__ save_invstd,
-                                                              float* __restrict__ save_count) {
+// forward: combine the slices' partials (sum (x - k_s), sum (x - k_s)^2; k_s = 0 for a slice that stored its raw pair, else its first row, re-read here) in fp64,
+// fixed order.  4 columns x 64 slice groups per workgroup.  Each slice is moved to ONE shift K per column, exactly up to fp64 roundings:
+//   sum (x - K) = sd + n (k_s - K),   sum (x - K)^2 = sd2 + 2 (k_s - K) sd + n (k_s - K)^2
+//   synced == 0 (per-rank statistics): K = 0; sums = (mean, biased variance, count), each the fp64 value rounded once -- except in a column all of whose slices stored
+//   raw pairs, where the two sums are rounded to fp32 first, as they always were: its mean and variance keep their bits;
+//   synced (SyncBatchNorm): K = shift[c] (the running mean, equal on every rank; 0 without one); sums = (sum (x - K), sum (x - K)^2, count), what the ranks add up.
+__global__ __launch_bounds__(256) void bn_combine_fwd_kernel(const float* __restrict__ part, const float* __restrict__ x, long R, long rps, int S, int C,
+                                                             const float* __restrict__ shift, int synced, float* __restrict__ sums) {
+  __shared__ double red[2][64][4];
+  __shared__ int rawred[64][4];
+  const int col = threadIdx.x & 3, grp = threadIdx.x >> 2;
+  const int c = blockIdx.x * 4 + col;
+  if (blockIdx.x == 0 && threadIdx.x == 0) sums[2 * C] = (float)R;
+  double a = 0.0, b = 0.0;
+  int allraw = 1;
+  if (c < C) {
+    const double K = (synced && shift) ? (double)shift[c] : 0.0;
+    for (int k = grp; k < S; k += 64) {
+      const long r0 = (long)k * rps;
+      if (r0 >= R) break;
+      const float p1 = part[((long)k * 2 + 1) * C + c];
+      const bool raw = __builtin_signbit(p1);
+      allraw &= raw ? 1 : 0;
+      const double n = (double)((r0 + rps > R ? R : r0 + rps) - r0), dk = (raw ? 0.0 : (double)x[r0 * C + c]) - K;
+      const double sd = part[((long)k * 2) * C + c], sd2 = raw ? -(double)p1 : (double)p1;
+      a += sd + n * dk;
+      b += sd2 + 2.0 * dk * sd + n * dk * dk;
+    }
+  }
+  red[0][grp][col] = a; red[1][grp][col] = b; rawred[grp][col] = allraw;
+  __syncthreads();
+  if (grp < 2) {
+    double t = 0.0;
+#pragma unroll 8
+    for (int g = 0; g < 64; ++g) t += red[grp][g][col];
+    red[grp][0][col] = t;          // (only this thread reads red[grp][.][col] after the barrier above)
+  }
+  __syncthreads();
+  if (grp == 0 && c < C) {
+    a = red[0][0][col]; b = red[1][0][col];
+    if (synced) { sums[c] = (float)a; sums[C + c] = (float)b; }
+    else {
+      for (int g = 1; g < 64; ++g) allraw &= rawred[g][col];
+      if (allraw) { a = (double)(float)a; b = (double)(float)b; }
+      const double m = a / (double)R;
+      double v = b / (double)R - m * m; if (v < 0.0) v = 0.0;
+      sums[c] = (float)m; sums[C + c] = (float)v;
+    }
+  }
+}
+// forward finalize: mean / biased var -> invstd, running statistics (unbiased var); eval mode: running statistics.  synced == 0: sums = (mean, var, count);
+// synced: sums = (sum (x - K), sum (x - K)^2, count) over all ranks with K = the running mean BEFORE this update (0 without one), as bn_combine_fwd_kernel formed them
+__global__ __launch_bounds__(256) void bn_finalize_fwd_kernel(const float* __restrict__ sums, int C, float eps, float momentum, int training, int synced,
+                                                              float* __restrict__ rmean, float* __restrict__ rvar, float* __restrict__ save_mean,
+                                                              float* __restrict__ save_invstd, float* __restrict__ save_count) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
   float mu, var;
   if (training) {
     const double R = (double)sums[2 * C];
-    const double m = (double)sums[c] / R;
-    double v = (double)sums[C + c] / R - m * m; if (v < 0.0) v = 0.0;
+    double m, v;
+    if (synced) {
+      const double d = (double)sums[c] / R;
+      v = (double)sums[C + c] / R - d * d; if (v < 0.0) v = 0.0;
+      m = (rmean ? (double)rmean[c] : 0.0) + d;
+    } else { m = (double)sums[c]; v = (double)sums[C + c]; }
     mu = (float)m; var = (float)v;
     if (rmean) rmean[c] = (1.0f - momentum) * rmean[c] + momentum * mu;
     if (rvar) rvar[c] = (1.0f - momentum) * rvar[c] + momentum * (R > 1.0 ? (float)(v * R / (R - 1.0)) : var);
@@ -336,7 +411,8 @@ int vdk_bn_rows_workspace_bytes(int64_t R, int32_t C, size_t* bytes) {
 }
 /* BatchNorm2d (+ residual, + ReLU) on NHWC rows: x f32 [R, C] -> out_bf16 and / or out_f32; training != 0: batch statistics (saved) and running update.
  * save_stats: f32 [2C + 1] = (mean, invstd, sample count).  sync != NULL (SyncBatchNorm, the reference's opt-in at engine/vision_engine.py:224-225): called on
- * the host with the device vector (sum x, sum x^2, count) [2C + 1] after its producer is enqueued; the callee enqueues a SUM all-reduce over the ranks. */
+ * the host with the device vector (sum (x - K), sum (x - K)^2, count) [2C + 1], K = running_mean before this update (0 without one), after its producer is
+ * enqueued; the callee enqueues a SUM all-reduce over the ranks. */
 int vdk_bn_act_fwd(const float* x, int64_t R, int32_t C, const float* gamma, const float* beta, float eps, float momentum, int32_t training, float* running_mean,
                    float* running_var, const float* res_f32, const void* res_bf16, int32_t relu, void* out_bf16, float* out_f32, float* save_mean, float* save_invstd,
                    void* ws, size_t ws_bytes, vdk_stat_sync_fn sync, void* user, void* stream_) {
@@ -351,13 +427,14 @@ int vdk_bn_act_fwd(const float* x, int64_t R, int32_t C, const float* gamma, con
   if (training) {
     hipLaunchKernelGGL(bn_partial_kernel<0>, dim3((unsigned)S, (unsigned)((C + 63) / 64)), dim3(512), 0, stream, x, (const float*)nullptr, (const bf16_t*)nullptr,
                        (const float*)nullptr, (const float*)nullptr, (long)R, (int)C, rps, part, opf_);
-    hipLaunchKernelGGL(bn_combine_kernel, dim3((unsigned)((2 * C + 15) / 16)), dim3(256), 0, stream, (const float*)part, S, (int)C, (float)R, sums);
+    hipLaunchKernelGGL(bn_combine_fwd_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, stream, (const float*)part, x, (long)R, rps, S, (int)C,
+                       (const float*)running_mean, sync ? 1 : 0, sums);
     if (sync) sync(user, sums, 2 * (int64_t)C + 1);
   }
   // the sample count is kept right behind invstd when the two save vectors are adjacent (engines allocate [2C + 1])
   float* save_count = (save_invstd == save_mean + C) ? save_invstd + C : nullptr;
-  hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, (const float*)sums, (int)C, eps, momentum, (int)training, running_mean,
-                     running_var, save_mean, save_invstd, save_count);
+  hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, (const float*)sums, (int)C, eps, momentum, (int)training,
+                     sync ? 1 : 0, running_mean, running_var, save_mean, save_invstd, save_count);
   const long n4 = R * C / 4;
   hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, x, n4, (int)C, gamma, beta, (const float*)save_mean,
                      (const float*)save_invstd, res_f32, (const bf16_t*)res_bf16, (int)relu, (bf16_t*)out_bf16, out_f32, opf_);

@@ -26,7 +26,8 @@ _BN_TALL_ROWS = 4096      # from this many rows on a per-rank BatchNorm runs as 
 
 
 def _bn_sync_cb(ws: torch.Tensor, group):
-    """vdk_stat_sync_fn of the neck's SyncBatchNorm: SUM all-reduce of the statistics vector the kernel sequence hands over (it lives inside `ws`)"""
+    """vdk_stat_sync_fn of the neck's SyncBatchNorm: SUM all-reduce of the statistics vector the kernel sequence hands over (it lives inside `ws`).  The forward's vector
+    holds moments about each rank's running_mean (include/visiondk.h, vdk_bn_act_fwd): the neck's BatchNorm buffers must be the same on every rank of the group"""
     import torch.distributed as dist
 
     def cb(user, ptr, n):
@@ -37,7 +38,7 @@ def _bn_sync_cb(ws: torch.Tensor, group):
 
 def _bn_rows_fwd(be, x, R, Cc, w, b, bn, training, y, sm, si, sync_group):
     """BatchNorm over R rows of x f32 [R, Cc] -> y f32.  sync_group False: the fused per-rank kernel; None / a process group (training): SyncBatchNorm -- statistics
-    kernel, all-reduce of (sum x, sum x^2, count), apply (the reference converts every BatchNorm when `sync_bn` is set, engine/vision_engine.py:224-225)."""
+    kernel, all-reduce of (sum (x - K), sum (x - K)^2, count) about K = the running mean, apply (the reference converts every BatchNorm when `sync_bn` is set, engine/vision_engine.py:224-225)."""
     tall = R >= _BN_TALL_ROWS and Cc % 4 == 0          # BatchNorm2d over the map's rows (25 088 x 1024 at cfg3): the slab-parallel kernel sequence; the one-kernel form walks each column with 16 row groups
     if (sync_group is False or not training) and not tall:
         be.check(be.lib.vdk_batchnorm1d_fwd(be.ptr(x), Cc, R, Cc, be.ptr(w), be.ptr(b), bn.eps, bn.momentum, int(training), be.ptr(bn.running_mean),

@@ -5,7 +5,9 @@ training step itself is orchestrated in C++ (csrc/vit_engine.hip).  No arithmeti
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import threading
 from typing import Optional
 
 import torch
@@ -640,34 +642,114 @@ def _bn_ws(be, R, Cc, device):
     return torch.empty(need.value, dtype=torch.uint8, device=device)
 
 
-def bn_act_fwd(x: torch.Tensor, gamma, beta, running_mean, running_var, *, training=True, eps=1e-5, momentum=0.1, res=None, relu=True, want_f32=False, backend=None):
-    """x f32 [R, C] -> (out bf16, out f32 | None, save_mean, save_invstd)"""
+_rn_format = threading.local()      # the calling thread's 16-bit format of the csrc/resnet_ops.hip functions, as vdk_resnet_ops_format keeps it
+
+
+def _rn16():
+    return getattr(_rn_format, "dtype", torch.bfloat16)
+
+
+@contextlib.contextmanager
+def resnet_ops_format(dtype, backend=None):
+    """the 16-bit format (torch.bfloat16 | torch.float16) of the NHWC / BatchNorm / pooling wrappers below inside the block.  On the way out bf16 is restored, not the
+    value before: do not nest it.  The wrappers allocate their 16-bit outputs by this module's own record of the format, which only this context manager updates: a direct
+    call of vdk_resnet_ops_format (or an engine's own guard) inside the block leaves the library and the wrappers out of step."""
+    be = _be(backend)
+    be.check(be.lib.vdk_resnet_ops_format(_dt(dtype)), "vdk_resnet_ops_format")
+    _rn_format.dtype = dtype
+    try:
+        yield
+    finally:
+        _rn_format.dtype = torch.bfloat16
+        be.check(be.lib.vdk_resnet_ops_format(_dt(torch.bfloat16)), "vdk_resnet_ops_format")
+
+
+def _bn_sync(ws, sync):
+    """vdk_stat_sync_fn around `sync(vector)`: the f32 view of the statistics vector inside `ws`, to be combined in place by work enqueued on the current stream"""
+    if sync is None:
+        return None
+
+    def cb(user, ptr, n):
+        off = ptr - ws.data_ptr()
+        sync(ws[off:off + 4 * n].view(torch.float32))
+    return _abi.STAT_SYNC_FN(cb)
+
+
+def bn_act_fwd(x: torch.Tensor, gamma, beta, running_mean, running_var, *, training=True, eps=1e-5, momentum=0.1, res=None, relu=True, want_f32=False, stats=None,
+               sync=None, backend=None):
+    """x f32 [R, C] -> (out 16-bit, out f32 | None, save_mean, save_invstd).  stats: f32 [2C + 1] that receives (mean, invstd, sample count) adjacent, as the engines
+    keep them (save_mean / save_invstd are then views of it); sync: callable(vector f32 [2C + 1]) = the SUM all-reduce of SyncBatchNorm (vdk_stat_sync_fn)"""
     be = _be(backend)
     R, Cc = x.shape
     ws = _bn_ws(be, R, Cc, x.device)
-    outb = torch.empty((R, Cc), dtype=torch.bfloat16, device=x.device)
+    outb = torch.empty((R, Cc), dtype=_rn16(), device=x.device)
     outf = torch.empty((R, Cc), dtype=torch.float32, device=x.device) if want_f32 else None
-    sm = torch.empty(Cc, dtype=torch.float32, device=x.device); si = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    if stats is not None:
+        assert stats.dtype == torch.float32 and stats.numel() == 2 * Cc + 1 and stats.is_contiguous()
+        sm, si = stats[:Cc], stats[Cc:2 * Cc]
+    else:
+        sm = torch.empty(Cc, dtype=torch.float32, device=x.device); si = torch.empty(Cc, dtype=torch.float32, device=x.device)
     rf = res if (res is not None and res.dtype == torch.float32) else None
-    rb = res if (res is not None and res.dtype == torch.bfloat16) else None
+    rb = res if (res is not None and res.dtype != torch.float32) else None
+    if rb is not None and rb.dtype != _rn16():
+        raise ValueError(f"16-bit residual must be {_rn16()}")
+    cb = _bn_sync(ws, sync)
     be.check(be.lib.vdk_bn_act_fwd(be.ptr(x), R, Cc, be.ptr(gamma), be.ptr(beta), eps, momentum, int(training), be.ptr(running_mean), be.ptr(running_var),
                                    be.ptr(rf) if rf is not None else None, be.ptr(rb) if rb is not None else None, int(relu), be.ptr(outb),
-                                   be.ptr(outf) if outf is not None else None, be.ptr(sm), be.ptr(si), be.ptr(ws), ws.numel(), None, None, be.stream()), "vdk_bn_act_fwd")
+                                   be.ptr(outf) if outf is not None else None, be.ptr(sm), be.ptr(si), be.ptr(ws), ws.numel(), cb, None, be.stream()), "vdk_bn_act_fwd")
     return outb, outf, sm, si
 
 
-def bn_act_bwd(x, dout, out_bf16, gamma, save_mean, save_invstd, want_dres=True, backend=None):
-    """-> (dy bf16 [R,C], dres f32 | None, dgamma, dbeta)"""
+def bn_act_bwd(x, dout, out_bf16, gamma, save_mean, save_invstd, want_dres=True, stats=None, sync=None, backend=None):
+    """-> (dy 16-bit [R,C], dres f32 | None, dgamma, dbeta).  stats: the forward's f32 [2C + 1] (save_mean / save_invstd are taken from it, the sample count behind them
+    tells the kernel whether the forward ran on the running statistics); sync: as bn_act_fwd, on (sum g, sum g x^, count)"""
     be = _be(backend)
     R, Cc = x.shape
     ws = _bn_ws(be, R, Cc, x.device)
-    dy = torch.empty((R, Cc), dtype=torch.bfloat16, device=x.device)
+    if stats is not None:
+        assert stats.dtype == torch.float32 and stats.numel() == 2 * Cc + 1 and stats.is_contiguous()
+        save_mean, save_invstd = stats[:Cc], stats[Cc:2 * Cc]
+    dy = torch.empty((R, Cc), dtype=_rn16(), device=x.device)
     dres = torch.empty((R, Cc), dtype=torch.float32, device=x.device) if want_dres else None
     dg = torch.empty(Cc, dtype=torch.float32, device=x.device); db = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    cb = _bn_sync(ws, sync)
     be.check(be.lib.vdk_bn_act_bwd(be.ptr(x), be.ptr(dout), be.ptr(out_bf16) if out_bf16 is not None else None, R, Cc, be.ptr(gamma), be.ptr(save_mean),
                                    be.ptr(save_invstd), be.ptr(dy), be.ptr(dres) if dres is not None else None, be.ptr(dg), be.ptr(db), be.ptr(ws), ws.numel(),
-                                   None, None, be.stream()), "vdk_bn_act_bwd")
+                                   cb, None, be.stream()), "vdk_bn_act_bwd")
     return dy, dres, dg, db
+
+
+def bn_rows_bwd(x, dout, gamma, save_mean, save_invstd, sync=None, backend=None):
+    """vdk_bn_act_bwd without a mask and with the input gradient in fp32 (the embedding neck's BatchNorm) -> (dx f32 [R, C], dgamma, dbeta)"""
+    be = _be(backend)
+    R, Cc = x.shape
+    ws = _bn_ws(be, R, Cc, x.device)
+    dx = torch.empty((R, Cc), dtype=torch.float32, device=x.device)
+    dg = torch.empty(Cc, dtype=torch.float32, device=x.device); db = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    cb = _bn_sync(ws, sync)
+    be.check(be.lib.vdk_bn_rows_bwd(be.ptr(x), be.ptr(dout), R, Cc, be.ptr(gamma), be.ptr(save_mean), be.ptr(save_invstd), be.ptr(dx), be.ptr(dg), be.ptr(db),
+                                    be.ptr(ws), ws.numel(), cb, None, be.stream()), "vdk_bn_rows_bwd")
+    return dx, dg, db
+
+
+def avgpool_fwd(x: torch.Tensor, bp: Optional[int] = None, backend=None) -> torch.Tensor:
+    """global average pool: x 16-bit [B, HW, C] -> 16-bit [bp, C] (rows >= B zero; bp defaults to B)"""
+    be = _be(backend)
+    B, HW, Cc = x.shape
+    bp = B if bp is None else bp
+    out = torch.empty((bp, Cc), dtype=x.dtype, device=x.device)
+    be.check(be.lib.vdk_avgpool_fwd(be.ptr(x), be.ptr(out), B, bp, HW, Cc, be.stream()), "vdk_avgpool_fwd")
+    return out
+
+
+def avgpool_bwd(dfeat: torch.Tensor, B: int, HW: int, Cc: int, backend=None) -> torch.Tensor:
+    """dfeat 16-bit [>= B, ld >= C] (rows contiguous in their first C entries) -> f32 [B * HW, C] = dfeat[b, c] / HW"""
+    be = _be(backend)
+    if dfeat.stride(1) != 1:
+        raise ValueError("dfeat rows must be contiguous")
+    dout = torch.empty((B * HW, Cc), dtype=torch.float32, device=dfeat.device)
+    be.check(be.lib.vdk_avgpool_bwd(dfeat.data_ptr(), dfeat.stride(0), be.ptr(dout), B, HW, Cc, be.stream()), "vdk_avgpool_bwd")
+    return dout
 
 
 def maxpool3s2(x_nhwc: torch.Tensor, want_argmax: bool = False, backend=None):

@@ -77,7 +77,9 @@ class ResNetEngine(FlatEngine):
         self._weights_version = self.params._version
 
     def _sync_cb(self, group):
-        """vdk_stat_sync_fn for SyncBatchNorm: all-reduce (SUM) the statistics vector the engine hands over; it lives inside the workspace tensor"""
+        """vdk_stat_sync_fn for SyncBatchNorm: all-reduce (SUM) the statistics vector the engine hands over; it lives inside the workspace tensor.  The forward's vector
+        holds moments about each rank's running_mean (include/visiondk.h, vdk_bn_act_fwd): the BatchNorm buffers must be the same on every rank of the group -- load a
+        checkpoint on all of them (DistributedDataParallel broadcasts buffers); a per-rank training forward outside the group leaves them apart"""
         if group is False:
             return _abi.STAT_SYNC_FN(0)
         import torch.distributed as dist
