@@ -286,6 +286,10 @@ INTERNAL = {
     "vdk_ls_residual_fwd": (C.c_int, [P, I64, P, I64, P, P, I64, I64, I32, I32, P]),
     "vdk_ls_residual_bwd_workspace_bytes": (C.c_int, [I64, I32, PSZ]),
     "vdk_ls_residual_bwd": (C.c_int, [P, I64, P, I64, P, P, I64, P, I64, I32, I32, P, SZ, P]),
+    "vdk_attention_bias_fwd_workspace_bytes": (C.c_int, [I32, I32, PSZ]),
+    "vdk_attention_bias_fwd": (C.c_int, [P, I64, P, I64, P, P, I32, I32, I32, I32, F32, I32, P, SZ, P]),
+    "vdk_attention_bias_bwd_workspace_bytes": (C.c_int, [I32, I32, I32, PSZ]),
+    "vdk_attention_bias_bwd": (C.c_int, [P, I64, P, P, I64, P, P, P, I64, P, I32, I32, I32, I32, F32, I32, P, SZ, P]),
     "vdk_cbir_range_workspace_bytes": (C.c_int, [I64, I64, I32, PSZ]),
     "vdk_cbir_range_count": (C.c_int, [P, I64, P, I32, P, P, I64, I32, F32, I32, P, P, SZ, P]),
     "vdk_cbir_range_fill": (C.c_int, [P, I64, P, I32, I64, I32, I64, P, I64, P, P, P, SZ, P]),

@@ -109,6 +109,17 @@ int vdk_mst_scan_workspace_bytes(int64_t nq, int64_t N, int32_t D, size_t* bytes
 int vdk_mst_scan_mask_layout(int64_t nq, int64_t N, int32_t D, size_t* offset_bytes, int64_t* pitch_words, int64_t* blocks);
 int vdk_mst_scan(const float* X, const void* Gb, const float* gnorm, const uint32_t* gmax_bits, const float* core, const int32_t* comp, int64_t N, int32_t D, int64_t q0,
                  int64_t nq, float* best_w, int32_t* best_j, void* ws, size_t ws_bytes, void* stream);
+/* Attention with an additive relative position bias over a whole short sequence (csrc/attention_bias.hip; the BEiT models): o = softmax(scale q k^T + bias[h]) v.
+ * qkv, o, dout, dqkv, lse, the pitches and dtype (VDK_BF16 | VDK_F16) as for vdk_attention_fwd_dt / vdk_attention_bwd_dt; bias f32 [H, N, N] (head, query, key), shared by
+ * every batch item; lse f32 [B, H, N] (fwd: may be NULL); dbias f32 [H, N, N] = the sum over the batch of dS, overwritten, the same bits on every run.  Served: 1 <= N <= 256
+ * and head_dim 64, anything else VDK_EUNSUPPORTED; a null pointer, a pitch that is short or no multiple of 8, a 16-bit tensor or workspace off a 16-byte boundary: VDK_EINVAL;
+ * a workspace below the *_workspace_bytes of the same shape: VDK_EWORKSPACE. */
+int vdk_attention_bias_fwd_workspace_bytes(int32_t N, int32_t H, size_t* bytes);
+int vdk_attention_bias_fwd(const void* qkv, int64_t ld, void* o, int64_t ldo, float* lse, const float* bias, int32_t B, int32_t N, int32_t H, int32_t head_dim, float scale,
+                           int32_t dtype, void* ws, size_t ws_bytes, void* stream);
+int vdk_attention_bias_bwd_workspace_bytes(int32_t B, int32_t N, int32_t H, size_t* bytes);
+int vdk_attention_bias_bwd(const void* qkv, int64_t ld, const void* o, const void* dout, int64_t ldo, const float* lse, const float* bias, void* dqkv, int64_t lddqkv,
+                           float* dbias, int32_t B, int32_t N, int32_t H, int32_t head_dim, float scale, int32_t dtype, void* ws, size_t ws_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

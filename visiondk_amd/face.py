@@ -2,7 +2,7 @@
 `FaceTrainingModel` / `FaceTrainingWrapper`, `FeatureExtractor`, and the `get_model` factory seam.
 
 Reference: models/faceX/backbone/timm_wrapper.py:5-54, models/faceX/face_model.py:10-54,88-143, models/smartmodel.py:5-10.
-Transformer backbones (timm ViT ids in visiondk_amd.vit.TIMM_VITS, DINOv2 ids in visiondk_amd.dinov2.TIMM_DINOV2S): neck LayerNorm(C) -> Flatten -> Linear(N*C, feat_dim) ->
+Transformer backbones (timm ViT ids in visiondk_amd.vit.TIMM_VITS, DINOv2 ids in visiondk_amd.dinov2.TIMM_DINOV2S, BEiT ids in visiondk_amd.beit.TIMM_BEITS): neck LayerNorm(C) -> Flatten -> Linear(N*C, feat_dim) ->
 BatchNorm1d(feat_dim) (timm_wrapper.py:39-47).  CNN backbones (timm ConvNeXt ids in visiondk_amd.convnext.TIMM_CONVNEXTS): neck
 BatchNorm2d(C) -> Flatten -> Linear(C*H*W, feat_dim) -> BatchNorm1d(feat_dim) (timm_wrapper.py:30-37).  state_dict keys equal the
 reference's: `model.<timm keys>`, `output_layer.0.*` (LayerNorm | BatchNorm2d), `output_layer.2.*` (Linear), `output_layer.3.*`."""
@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _abi, _lib, convnext, dinov2, heads, ops, resnet, swin, swinv2, vit
+from . import _abi, _lib, beit, convnext, dinov2, heads, ops, resnet, swin, swinv2, vit
 
 
 def _up(x, a):
@@ -256,9 +256,15 @@ class TimmWrapper(nn.Module):
             self.model = dinov2.create_model(model_name, pretrained=False, num_classes=0, global_pool="", img_size=image_size, device=dev, backend=self.be, operand=operand)
             tokens, channels = self.model.tokens, self.model.spec.dim
             self.output_layer = nn.Sequential(nn.LayerNorm(channels), nn.Flatten(1), nn.Linear(tokens * channels, feat_dim), nn.BatchNorm1d(feat_dim)).to(dev)
+        elif model_name in beit.TIMM_BEITS:
+            # BEiT / BEiT-v2 B/L patch16_224 (LayerScale + relative position bias): the normed tokens [B, N, D] go into the transformer neck, as for DINOv2; autograd-node
+            # form, so FaceTrainStep and forward_precise refuse it.
+            self.model = beit.create_model(model_name, pretrained=False, num_classes=0, global_pool="", img_size=image_size, device=dev, backend=self.be, operand=operand)
+            tokens, channels = self.model.tokens, self.model.spec.dim
+            self.output_layer = nn.Sequential(nn.LayerNorm(channels), nn.Flatten(1), nn.Linear(tokens * channels, feat_dim), nn.BatchNorm1d(feat_dim)).to(dev)
         else:
             raise NotImplementedError(f"backbone '{model_name}': the HIP engines cover {sorted(vit.TIMM_VITS)}, {sorted(convnext.TIMM_CONVNEXTS)} and {sorted(swin.TIMM_SWINS)}"
-                                      f"; as autograd nodes over the kernels: {sorted(swinv2.TIMM_SWINV2S)} and {sorted(dinov2.TIMM_DINOV2S)}")
+                                      f"; as autograd nodes over the kernels: {sorted(swinv2.TIMM_SWINV2S)}, {sorted(dinov2.TIMM_DINOV2S)} and {sorted(beit.TIMM_BEITS)}")
 
     @torch.no_grad()
     def forward_precise(self, x):
@@ -269,6 +275,8 @@ class TimmWrapper(nn.Module):
             raise NotImplementedError(_SWINV2_NEEDS_ENGINE.format(what="forward_precise (fp32-MFMA evaluation)"))
         if isinstance(self.model, dinov2.DinoVisionTransformer):
             raise NotImplementedError(dinov2.NEEDS_ENGINE.format(what="forward_precise (fp32-MFMA evaluation)"))
+        if isinstance(self.model, beit.Beit):
+            raise NotImplementedError(beit.NEEDS_ENGINE.format(what="forward_precise (fp32-MFMA evaluation)"))
         if not hasattr(self.model, "forward_precise"):
             raise NotImplementedError("forward_precise (fp32-MFMA evaluation) is built for the native ViT, ConvNeXt and Swin engines; this backbone object has none")
         feat = self.model.forward_precise(x)
@@ -430,7 +438,8 @@ class VisionWrapper:
         arch = name[5:].split(".")[0]
         # timm-resnet18 | timm-convnext_* (pet.yaml:21-22) | timm-vit_*
         factory = (resnet.create_model if arch in resnet.TIMM_RESNETS else convnext.create_model if arch in convnext.TIMM_CONVNEXTS else
-                   swin.create_model if arch in swin.TIMM_SWINS else swinv2.create_model if arch.startswith("swinv2_") else dinov2.create_model if "dinov2" in arch else vit.create_model)      # timm-swin_base_patch4_window7_224 is pet.yaml:25's default; every
+                   swin.create_model if arch in swin.TIMM_SWINS else swinv2.create_model if arch.startswith("swinv2_") else dinov2.create_model if "dinov2" in arch else
+                   beit.create_model if arch.startswith(("beit_", "beitv2_")) else vit.create_model)      # timm-swin_base_patch4_window7_224 is pet.yaml:25's default; every
         #                                                                                     swinv2_ id goes to swinv2.create_model, whose KeyError lists the served window-8 ids; every
         #                                                                                     dinov2 id likewise to dinov2.create_model (ViT-S/B/L/14 served; giant / reg4 a KeyError)
         self.model = factory(arch, pretrained=False, num_classes=model_cfg["num_classes"], img_size=model_cfg.get("image_size") or 224, device=device,
@@ -494,6 +503,8 @@ class FaceTrainStep:
             raise NotImplementedError(_SWINV2_NEEDS_ENGINE.format(what="FaceTrainStep"))
         if isinstance(self.bb.model, dinov2.DinoVisionTransformer):
             raise NotImplementedError(dinov2.NEEDS_ENGINE.format(what="FaceTrainStep"))
+        if isinstance(self.bb.model, beit.Beit):
+            raise NotImplementedError(beit.NEEDS_ENGINE.format(what="FaceTrainStep"))
         if not hasattr(self.bb.model, "engine"):
             raise NotImplementedError("FaceTrainStep needs a backbone with a native engine (ViT, ConvNeXt, Swin with native=True); the autograd-node Swin trains under "
                                       "the reference's own Trainer (torch optimizer over model.parameters())")

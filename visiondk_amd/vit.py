@@ -492,6 +492,9 @@ class FusedTrainStep:
         if type(model).__name__ == "DinoVisionTransformer":
             from . import dinov2
             raise NotImplementedError(dinov2.NEEDS_ENGINE.format(what="FusedTrainStep"))
+        if type(model).__name__ == "Beit":
+            from . import beit
+            raise NotImplementedError(beit.NEEDS_ENGINE.format(what="FusedTrainStep"))
         if not hasattr(model, "engine"):
             raise NotImplementedError("FusedTrainStep needs a native engine; SwinV2 (swinv2_*_window8_256) is served as autograd nodes over the kernels and trains under a plain "
                                       "torch optimizer over model.parameters() (with a loss scale for fp16 operands).  The native vdk_swinv2_* engine is a follow-up.")
